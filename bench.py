@@ -4,7 +4,14 @@ context, RQ-spline, batch 2^20, 1 MI355X"; shapes pinned in SURVEY.md §8: K=8, 
 split 8, tanh, bound 3).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--scaling strong|weak]
-                    [--no-cpu-baseline] [--train | --cnf | --flow F | --bayes M]
+                    [--full [--no-cpu-baseline]] [--dump-outputs DIR]
+                    [--train | --cnf | --flow F | --bayes M] [--no-cpu-baseline]
+
+A plain run sets up, warms up, times --steps steps and prints the result line.  ``--full`` adds
+the headline's other legs (the same steps through NormalizingFlow.log_prob, the host CPU baseline,
+the parity spot check against the fp64 oracle); ``--dump-outputs DIR`` writes the last timed
+step's log_prob rows to DIR/log_prob.npy (the inputs are seeded: the same arguments give the
+same rows).
 
 One step = one fused log_prob launch over this rank's rows, inputs resident in HBM.  N > 1
 runs one process per GPU: under torch.distributed.run (RANK/WORLD_SIZE set by the driver), or,
@@ -263,6 +270,24 @@ def warm_up(step, args, dev):
         torch.cuda.synchronize(dev)
         if time.perf_counter() - t0 >= WARM_MIN_S:
             return n
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: write each output of the last timed step as <out_dir>/<name>.npy (float32).
+    An output that would take the files past DUMP_MAX_BYTES is cut to a fixed sample of its leading
+    dimension (sorted indices drawn without replacement from numpy's default_rng(0))."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget:
+            keep = budget // (a.nbytes // a.shape[0])
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))]
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a))
 
 
 def run_train(args, dev, rank, world, dist):
@@ -1141,6 +1166,15 @@ def main():
     ap.add_argument("--micro-batch", type=int, default=1 << 22,  # (2^20: 170-174 ms per step, 2^22: 157-164, r06_g3/g7)
                     help="--train: rows per forward+backward chunk (gradients accumulate before the all-reduce)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="the headline run also times the same steps through NormalizingFlow.log_prob "
+                         "(api_log_prob), the host CPU baseline (cpu_baseline, unless --no-cpu-baseline) and "
+                         "checks 4096 rows against the fp64 oracle (parity_spot_check); off by default: a plain "
+                         "run sets up, warms up, times --steps steps and prints the result line (the other modes "
+                         "always run all their legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (this rank's log_prob "
+                         "rows, float32) as DIR/log_prob.npy (DIR/log_prob_rank<r>.npy when N > 1)")
     ap.add_argument("--graph", action="store_true",
                     help="--train --flow: replay the whole NLL step as one captured HIP graph (trainers.GraphedNllStep)")
     ap.add_argument("--train-walk", action="store_true",
@@ -1172,6 +1206,9 @@ def main():
                     help="auto (default): f16x3r16 (16-row waves) when the packed hidden-layer weights fit fp16 and "
                          "the shape allows, else f16x3, else bf16x6; f32: exact FP32 MFMA")
     args = ap.parse_args()
+    if args.dump_outputs and (args.train or args.cnf or args.cnf_train or args.flow or args.bayes):
+        ap.error("--dump-outputs belongs to the headline log_prob run (no --train / --cnf / --cnf-train / --flow / "
+                 "--bayes)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -1257,26 +1294,30 @@ def run_log_prob(args, dev, rank, world, dist):
     elapsed = time.perf_counter() - t0
     kern_ms = [a.elapsed_time(b) for a, b in evs]
     avg_kern_s = sum(kern_ms) / len(kern_ms) / 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"log_prob" if world == 1 else f"log_prob_rank{rank}": out})
 
-    # the same K steps through the Python front end naz callers use (NormalizingFlow.log_prob,
-    # naz flow.py:45-79: condition, distribution, pack-version check, output allocation), timed the
-    # same way after the raw-ABI loop
-    with torch.no_grad():
-        for _ in range(2):
-            flow.log_prob(x, condition=c)
-        torch.cuda.synchronize(dev)
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize(dev)
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            lp_api = flow.log_prob(x, condition=c)
-        torch.cuda.synchronize(dev)
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize(dev)
-        api_elapsed = time.perf_counter() - t1
-    api_same = bool(torch.equal(lp_api, out))
+    api_elapsed = 0.0
+    if args.full:
+        # the same K steps through the Python front end naz callers use (NormalizingFlow.log_prob,
+        # naz flow.py:45-79: condition, distribution, pack-version check, output allocation), timed the
+        # same way after the raw-ABI loop
+        with torch.no_grad():
+            for _ in range(2):
+                flow.log_prob(x, condition=c)
+            torch.cuda.synchronize(dev)
+            if dist is not None:
+                dist.barrier()
+            torch.cuda.synchronize(dev)
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                lp_api = flow.log_prob(x, condition=c)
+            torch.cuda.synchronize(dev)
+            if dist is not None:
+                dist.barrier()
+            torch.cuda.synchronize(dev)
+            api_elapsed = time.perf_counter() - t1
+        api_same = bool(torch.equal(lp_api, out))
 
     if dist is not None:
         t = torch.tensor([elapsed, avg_kern_s, api_elapsed], device=dev, dtype=torch.float64)
@@ -1326,11 +1367,13 @@ def run_log_prob(args, dev, rank, world, dist):
                                    mode, "coupling_x6_kernel") + f"<16,32,8,8,128,lower,inv,{mode}>",
                          "flop_per_row": flops_per_row(), "avg_kernel_ms": avg_kern_s * 1e3,
                          "hbm_alg_GBps": bytes_per_row() * B / avg_kern_s / 1e9},
-            "api_log_prob": {"path": "NormalizingFlow.log_prob(x, condition=ctx) under torch.no_grad (naz flow.py:45-79)",
-                             "ms_per_step": api_elapsed / args.steps * 1e3, "value": total_rows / api_elapsed,
-                             "unit": "samples/s", "same_result_as_abi": api_same},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            rec["api_log_prob"] = {
+                "path": "NormalizingFlow.log_prob(x, condition=ctx) under torch.no_grad (naz flow.py:45-79)",
+                "ms_per_step": api_elapsed / args.steps * 1e3, "value": total_rows / api_elapsed,
+                "unit": "samples/s", "same_result_as_abi": api_same}
+        if args.full and world == 1 and not args.no_cpu_baseline:
             base, parity = cpu_baseline(flow, x_host, c_host)
             rec["cpu_baseline"] = base
             rec["parity_spot_check"] = parity

@@ -22,6 +22,6 @@ run() {  # run <name> <timeout> <cmd...>
 STEPS=${STEPS:-smoke,tests,bench,prof}
 [[ $STEPS == *smoke* ]] && run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 [[ $STEPS == *tests* ]] && run gpu_tests 420 python -m pytest tests -m gpu -x -q -rA
-[[ $STEPS == *bench* ]] && run bench 240 python bench.py
+[[ $STEPS == *bench* ]] && run bench 240 python bench.py --full
 [[ $STEPS == *prof* ]] && run prof 200 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o run --output-format csv -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline
 exit 0

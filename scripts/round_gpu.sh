@@ -15,7 +15,7 @@ step() {  # step <name> <timeout> <cmd...>; stop on crash / timeout
   echo "rc=$rc"; tail -n 2 "$O/$name.log" | cut -c1-400
   if [ $rc -ne 0 ]; then echo "stopping after $name"; exit $rc; fi
 }
-step bench 300 python bench.py
+step bench 300 python bench.py --full
 step prof 240 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 10 --no-cpu-baseline
 step pmc_fetch 120 rocprofv3 --pmc FETCH_SIZE -d $O/pmc/p1 -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
 step pmc_write 120 rocprofv3 --pmc WRITE_SIZE -d $O/pmc/p2 -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
