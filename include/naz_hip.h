@@ -100,6 +100,24 @@ int naz_rqs_fwd(const float* x, int64_t ldx, const float* raw, int64_t ldr, floa
 int naz_rqs_inv(const float* x, int64_t ldx, const float* raw, int64_t ldr, float* y, int64_t ldy, float* ld,
                 int ld_mode, int64_t B, int Dt, int K, int layout, float bound, void* stream);
 
+/* ---- a1+a2, order="linear": the rational-LINEAR spline ------------------------------
+ * [pyro] _monotonic_rational_spline(order="linear"), naz's `order` keyword
+ * (naz/flows/transforms.py:165-171, 201-212).  Same arguments, layouts, ld modes, NAZ_RQS_FAST
+ * flag and host checks as naz_rqs_fwd / naz_rqs_inv / naz_rqs_bwd; raw and g_raw rows are
+ * Dt*(4K-1) wide, the fourth block being the per-bin split position's unnormalised λ
+ * (without NAZ_RQS_FAST the map is evaluated in double and rounded once: the training walk):
+ *   NAZ_LAYOUT_DENSE  [w(Dt*K) | h(Dt*K) | d(Dt*(K-1)) | l(Dt*K)]
+ *   NAZ_LAYOUT_ARN    column p*Dt + i, p in [0, 4K-1): w p=k, h p=K+k, d p=2K+k, l p=3K-1+k
+ * ldr = 0 shares one parameter row (a linear-order lower spline); naz_rls_bwd then
+ * ACCUMULATES g_raw [Dt*(4K-1)] over the batch.                                          */
+int naz_rls_fwd(const float* x, int64_t ldx, const float* raw, int64_t ldr, float* y, int64_t ldy, float* ld,
+                int ld_mode, int64_t B, int Dt, int K, int layout, float bound, void* stream);
+int naz_rls_inv(const float* x, int64_t ldx, const float* raw, int64_t ldr, float* y, int64_t ldy, float* ld,
+                int ld_mode, int64_t B, int Dt, int K, int layout, float bound, void* stream);
+int naz_rls_bwd(int inverse, const float* x, int64_t ldx, const float* raw, int64_t ldr, const float* g_out,
+                int64_t ldgo, const float* g_ld, int g_ld_mode, float* g_in, int64_t ldgi, float* g_raw, int64_t ldgr,
+                int64_t B, int Dt, int K, int layout, float bound, void* stream);
+
 /* ---- a1: unconditional elementwise spline ([pyro] Spline, the coupling's lower
  * spline, naz/flows/transforms.py:128 intent).  uw/uh [Dt,K], ud [Dt,K-1] are the
  * UNNORMALISED parameters; ld is per-dim [B, Dt].                                   */

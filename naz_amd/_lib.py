@@ -53,6 +53,8 @@ SIGNATURES = {
     "naz_debug_nonfinite": (C.c_int, [C.POINTER(C.c_int64), _i]),
     "naz_rqs_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i64, _i, _i, _i, C.c_float, _vp]),
     "naz_rqs_inv": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i64, _i, _i, _i, C.c_float, _vp]),
+    "naz_rls_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i64, _i, _i, _i, C.c_float, _vp]),
+    "naz_rls_inv": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i64, _i, _i, _i, C.c_float, _vp]),
     "naz_spline_elementwise": (C.c_int, [_i, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _i, C.c_float,
                                          _vp]),
     "naz_linear_act": (C.c_int, [_vp, _i64, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _vp]),
@@ -69,6 +71,8 @@ SIGNATURES = {
     "naz_bounding_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp]),
     "naz_bounding_inv": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i, _vp]),
     "naz_rqs_bwd": (C.c_int, [_i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _vp, _i64, _vp, _i64, _i64, _i, _i, _i,
+                              C.c_float, _vp]),
+    "naz_rls_bwd": (C.c_int, [_i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _vp, _i64, _vp, _i64, _i64, _i, _i, _i,
                               C.c_float, _vp]),
     "naz_gemm": (C.c_int, [_i, _i, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i, _i,
                            _i, _vp, _vp]),

@@ -208,23 +208,26 @@ class RqsFn(Function):
     direction: the forward ldf, or the inverse's -ldf)."""
 
     @staticmethod
-    def forward(ctx, x, raw, count_bins: int, layout: int, inverse: bool, bound: float, broadcast: bool):
-        y, ld = ops.rqs(x, raw, count_bins, layout, inverse, bound, ops.LD_ROWSUM, broadcast_raw=broadcast)
-        ctx.cfg = (count_bins, layout, inverse, bound, broadcast)
+    def forward(ctx, x, raw, count_bins: int, layout: int, inverse: bool, bound: float, broadcast: bool,
+                order: str = "quadratic"):
+        y, ld = ops.rqs(x, raw, count_bins, layout, inverse, bound, ops.LD_ROWSUM, broadcast_raw=broadcast,
+                        order=order)
+        ctx.cfg = (count_bins, layout, inverse, bound, broadcast, order)
         ctx.save_for_backward(x, raw)
         return y, ld
 
     @staticmethod
     def backward(ctx, g_y, g_ld):
         x, raw = ctx.saved_tensors
-        K, layout, inverse, bound, broadcast = ctx.cfg
+        K, layout, inverse, bound, broadcast, order = ctx.cfg
         g_x, g_raw = ops.rqs_bwd(x, raw, K, layout, inverse, bound, g_y, g_ld, need_g_in=_needs(ctx, 0),
-                                 broadcast_raw=broadcast)
-        return g_x, g_raw, None, None, None, None, None
+                                 broadcast_raw=broadcast, order=order)
+        return g_x, g_raw, None, None, None, None, None, None
 
 
-def rqs(x, raw, count_bins, layout=ops.LAYOUT_DENSE, inverse=False, bound=3.0, broadcast=False):
-    return RqsFn.apply(x, raw, count_bins, layout, inverse, bound, broadcast)
+def rqs(x, raw, count_bins, layout=ops.LAYOUT_DENSE, inverse=False, bound=3.0, broadcast=False,
+        order="quadratic"):
+    return RqsFn.apply(x, raw, count_bins, layout, inverse, bound, broadcast, order)
 
 
 class AffineARFn(Function):

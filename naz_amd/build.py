@@ -24,7 +24,7 @@ ARCH = os.environ.get("NAZ_OFFLOAD_ARCH", "gfx950")
 # packing moves add register pressure (spills in coupling_x6_kernel with it on).
 SOURCE_FLAGS = {"coupling.hip": ["-fno-slp-vectorize"], "cnf.hip": ["-fno-slp-vectorize"],
                 "made.hip": ["-fno-slp-vectorize"]}
-SOURCES = ["rqs.hip", "dense.hip", "gemm.hip", "gemm_rows.hip", "elementwise.hip", "made.hip", "coupling.hip", "cnf.hip", "capi.cpp"]
+SOURCES = ["rqs.hip", "rls.hip", "dense.hip", "gemm.hip", "gemm_rows.hip", "elementwise.hip", "made.hip", "coupling.hip", "cnf.hip", "capi.cpp"]
 # sources compiled more than once with a part macro (object name suffix, extra flags): coupling.hip
 # holds the coupling, the autoregressive and the autoregressive-backward kernels, ~5 min of device
 # compile in one object

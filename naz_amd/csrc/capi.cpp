@@ -342,6 +342,29 @@ int naz_rqs_bwd(int inverse, const float* x, int64_t ldx, const float* raw, int6
                  bound, as_stream(stream));
 }
 
+int naz_rls_fwd(const float* x, int64_t ldx, const float* raw, int64_t ldr, float* y, int64_t ldy, float* ld,
+                int ld_mode, int64_t B, int Dt, int K, int layout, float bound, void* stream) {
+  if (int rc = check_spline_args("naz_rls_fwd", x, y, B, Dt, K, bound)) return rc;
+  return rls_cond(0, x, ldx, raw, ldr, y, ldy, ld, ld_mode, B, Dt, K, layout, bound, as_stream(stream));
+}
+
+int naz_rls_inv(const float* x, int64_t ldx, const float* raw, int64_t ldr, float* y, int64_t ldy, float* ld,
+                int ld_mode, int64_t B, int Dt, int K, int layout, float bound, void* stream) {
+  if (int rc = check_spline_args("naz_rls_inv", x, y, B, Dt, K, bound)) return rc;
+  return rls_cond(1, x, ldx, raw, ldr, y, ldy, ld, ld_mode, B, Dt, K, layout, bound, as_stream(stream));
+}
+
+int naz_rls_bwd(int inverse, const float* x, int64_t ldx, const float* raw, int64_t ldr, const float* g_out,
+                int64_t ldgo, const float* g_ld, int g_ld_mode, float* g_in, int64_t ldgi, float* g_raw, int64_t ldgr,
+                int64_t B, int Dt, int K, int layout, float bound, void* stream) {
+  if (int rc = check_spline_args("naz_rls_bwd", x, x, B, Dt, K, bound)) return rc;
+  if (B > 0 && g_raw == nullptr) return set_error("naz_rls_bwd: g_raw is required");
+  if (g_ld_mode < 0 || g_ld_mode > 2 || (g_ld_mode != 0 && g_ld == nullptr))
+    return set_error("naz_rls_bwd: bad g_ld / g_ld_mode");
+  return rls_bwd(inverse, x, ldx, raw, ldr, g_out, ldgo, g_ld, g_ld_mode, g_in, ldgi, g_raw, ldgr, B, Dt, K, layout,
+                 bound, as_stream(stream));
+}
+
 int naz_gemm(int M, int N, int64_t K, const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk,
              int64_t sbn, float* C, int64_t scm, int64_t scn, const float* mask, int64_t smm, int64_t smn,
              int mask_b, int accumulate, int split_k, float* rowsum, void* stream) {

@@ -21,6 +21,7 @@ constexpr float kMinBinWidth = 1e-3f;
 constexpr float kMinBinHeight = 1e-3f;
 constexpr float kMinDerivative = 1e-3f;
 constexpr float kSearchEps = 1e-6f;
+constexpr float kMinLambda = 0.025f;  // rational-linear spline (rls.hip): λ ∈ [min, 1 − min]
 
 // Publish an LDS-DMA ring slot.  A global_load_lds write is pending on the issuing wave's
 // vmcnt until it lands in LDS; __syncthreads() alone does NOT reliably drain it: on a loop
@@ -39,6 +40,23 @@ NAZ_DEV void ring_barrier() {
   __builtin_amdgcn_s_waitcnt(0x0F70);
 #endif
   __syncthreads();
+}
+
+// Copy `n` floats starting at src[0] into lds[0..n) with 16-B loads where aligned.
+NAZ_DEV void block_copy_to_lds(float* lds, const float* __restrict__ src, int n, int tid, int nthreads) {
+  uintptr_t addr = reinterpret_cast<uintptr_t>(src);
+  int head = (int)(((16 - (addr & 15)) & 15) >> 2);
+  if ((addr & 3) != 0) head = n;  // not even 4-B aligned: scalar path
+  if (head > n) head = n;
+  for (int i = tid; i < head; i += nthreads) lds[i] = src[i];
+  int nvec = (n - head) >> 2;
+  const float4* s4 = reinterpret_cast<const float4*>(src + head);
+  for (int i = tid; i < nvec; i += nthreads) {
+    float4 v = s4[i];
+    int o = head + 4 * i;
+    lds[o + 0] = v.x; lds[o + 1] = v.y; lds[o + 2] = v.z; lds[o + 3] = v.w;
+  }
+  for (int i = head + 4 * nvec + tid; i < n; i += nthreads) lds[i] = src[i];
 }
 
 enum Act : int { ACT_IDENTITY = 0, ACT_TANH = 1, ACT_RELU = 2, ACT_SOFTPLUS = 3, ACT_SIGMOID = 4 };

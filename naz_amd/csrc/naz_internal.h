@@ -12,9 +12,30 @@ int set_error(const char* fmt, ...);
 // Checks hipGetLastError after a launch; sets the message and returns nonzero on failure.
 int check_launch(const char* what);
 
+// Dispatch on the instantiated bin counts of the spline kernels (rqs.hip, rls.hip).
+#define NAZ_K_DISPATCH(K_, CALL) \
+  switch (K_) {                  \
+    case 2: CALL(2); break;      \
+    case 3: CALL(3); break;      \
+    case 4: CALL(4); break;      \
+    case 5: CALL(5); break;      \
+    case 6: CALL(6); break;      \
+    case 8: CALL(8); break;      \
+    case 10: CALL(10); break;    \
+    case 12: CALL(12); break;    \
+    case 16: CALL(16); break;    \
+    default: return set_error("naz_rqs: count_bins=%d not instantiated (2,3,4,5,6,8,10,12,16)", K_); \
+  }
+
 int rqs_cond(int inverse, const float* x, int64_t ldx, const float* raw, int64_t ldr, float* y, int64_t ldy,
              float* ld, int ld_mode, int64_t B, int Dt, int K, int layout, float bound, hipStream_t s);
 int rqs_bwd(int inverse, const float* x, int64_t ldx, const float* raw, int64_t ldr, const float* g_out, int64_t ldgo,
+            const float* g_ld, int g_ld_mode, float* g_in, int64_t ldgi, float* g_raw, int64_t ldgr, int64_t B, int Dt,
+            int K, int layout, float bound, hipStream_t s);
+// rational-linear spline (rls.hip): rqs_cond / rqs_bwd's arguments, raw rows Dt*(4K-1) wide
+int rls_cond(int inverse, const float* x, int64_t ldx, const float* raw, int64_t ldr, float* y, int64_t ldy,
+             float* ld, int ld_mode, int64_t B, int Dt, int K, int layout, float bound, hipStream_t s);
+int rls_bwd(int inverse, const float* x, int64_t ldx, const float* raw, int64_t ldr, const float* g_out, int64_t ldgo,
             const float* g_ld, int g_ld_mode, float* g_in, int64_t ldgi, float* g_raw, int64_t ldgr, int64_t B, int Dt,
             int K, int layout, float bound, hipStream_t s);
 int rqs_uncond(int inverse, const float* x, int64_t ldx, const float* uw, const float* uh, const float* ud, float* y,

@@ -26,23 +26,6 @@
 
 namespace naz {
 
-// Copy `n` floats starting at src[0] into lds[0..n) with 16-B loads where aligned.
-NAZ_DEV void block_copy_to_lds(float* lds, const float* __restrict__ src, int n, int tid, int nthreads) {
-  uintptr_t addr = reinterpret_cast<uintptr_t>(src);
-  int head = (int)(((16 - (addr & 15)) & 15) >> 2);
-  if ((addr & 3) != 0) head = n;  // not even 4-B aligned: scalar path
-  if (head > n) head = n;
-  for (int i = tid; i < head; i += nthreads) lds[i] = src[i];
-  int nvec = (n - head) >> 2;
-  const float4* s4 = reinterpret_cast<const float4*>(src + head);
-  for (int i = tid; i < nvec; i += nthreads) {
-    float4 v = s4[i];
-    int o = head + 4 * i;
-    lds[o + 0] = v.x; lds[o + 1] = v.y; lds[o + 2] = v.z; lds[o + 3] = v.w;
-  }
-  for (int i = head + 4 * nvec + tid; i < n; i += nthreads) lds[i] = src[i];
-}
-
 template <int K, bool INV, bool FAST>
 __global__ void __launch_bounds__(256) rqs_cond_kernel(
     const float* __restrict__ x, int64_t ldx, const float* __restrict__ raw, int64_t ldr,
@@ -244,20 +227,6 @@ static int launch_rqs_bwd(const float* x, int64_t ldx, const float* raw, int64_t
                        g_out, ldgo, g_ld, g_ld_mode, g_in, ldgi, g_raw, ldgr, B, Dt, layout, bound);
   return check_launch("rqs_bwd_kernel");
 }
-
-#define NAZ_K_DISPATCH(K_, CALL) \
-  switch (K_) {                  \
-    case 2: CALL(2); break;      \
-    case 3: CALL(3); break;      \
-    case 4: CALL(4); break;      \
-    case 5: CALL(5); break;      \
-    case 6: CALL(6); break;      \
-    case 8: CALL(8); break;      \
-    case 10: CALL(10); break;    \
-    case 12: CALL(12); break;    \
-    case 16: CALL(16); break;    \
-    default: return set_error("naz_rqs: count_bins=%d not instantiated (2,3,4,5,6,8,10,12,16)", K_); \
-  }
 
 int rqs_cond(int inverse, const float* x, int64_t ldx, const float* raw, int64_t ldr, float* y, int64_t ldy,
              float* ld, int ld_mode, int64_t B, int Dt, int K, int layout, float bound, hipStream_t s) {

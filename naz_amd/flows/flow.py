@@ -555,6 +555,8 @@ def _fused_plan(flow_type, flow_args, flow_kwargs, transforms):
     a = _maker_args(flow_type, flow_args, flow_kwargs)
     if a is None or "theta_dim" not in a:
         return None
+    if a.get("order", "quadratic") != "quadratic":
+        return None  # the fused whole-flow kernels evaluate the quadratic spline; linear runs per kernel
     if flow_type in ("nsa", "maf") and _AR_FUSED != "0":
         D, C, hidden, L = a["theta_dim"], a["condition_dim"], a["hidden_dim"], a["num_layers"]
         K = a["count_bins"] if flow_type == "nsa" else 8

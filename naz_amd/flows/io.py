@@ -4,6 +4,7 @@ The canonical state is a flat dict of arrays, one entry per tensor, per layer ``
   layers.{l}.nn.layers.{i}.weight / .bias          conditioner (pyro names, train_flows.py:414)
   layers.{l}.nn.permutation                        MADE variable order (maf / nsa)
   layers.{l}.lower_spline.unnormalized_{widths,heights,derivatives}   coupling lower spline
+  layers.{l}.lower_spline.unnormalized_lambdas     ... of an order="linear" flow only
 It is what ``torch_to_jax`` (naz/flows/bflow_jax_maf.py:26-46) extracts from a pyro flow,
 so an offline exporter run where pyro exists can feed trained naz flows to naz_amd.
 Saved as ``.npz`` (no pickle).
@@ -39,6 +40,12 @@ def _lower(t):
     return getattr(t, "lower_spline", None)
 
 
+def _lower_names(low):
+    """The lower spline's parameter names: pyro's three, plus the lambdas of a linear-order spline."""
+    names = ("widths", "heights", "derivatives")
+    return names + ("lambdas",) if hasattr(low, "unnormalized_lambdas") else names
+
+
 def named_state_params(flow) -> Dict[str, torch.nn.Parameter]:
     """Canonical key -> the live trainable tensor (what get_params/set_params in
     naz/trainers/train_flows.py:20-71 walk; gradients are read back by the same keys)."""
@@ -50,7 +57,7 @@ def named_state_params(flow) -> Dict[str, torch.nn.Parameter]:
             out[p + f"nn.layers.{i}.bias"] = lin.bias
         low = _lower(t)
         if low is not None:
-            for n in ("widths", "heights", "derivatives"):
+            for n in _lower_names(low):
                 out[p + "lower_spline.unnormalized_" + n] = getattr(low, "unnormalized_" + n)
     return out
 
@@ -66,7 +73,7 @@ def export_state(flow) -> Dict[str, np.ndarray]:
             out[p + "nn.permutation"] = t.nn.permutation.detach().cpu().numpy().astype(np.int64)
         low = _lower(t)
         if low is not None:
-            for n in ("widths", "heights", "derivatives"):
+            for n in _lower_names(low):
                 out[p + "lower_spline.unnormalized_" + n] = getattr(low, "unnormalized_" + n).detach().cpu().numpy()
     return out
 
@@ -83,7 +90,7 @@ def load_state(flow, state: Dict[str, np.ndarray]) -> None:
             lin.bias.copy_(torch.as_tensor(np.asarray(state[p + f"nn.layers.{i}.bias"])))
         low = _lower(t)
         if low is not None:
-            for n in ("widths", "heights", "derivatives"):
+            for n in _lower_names(low):
                 getattr(low, "unnormalized_" + n).copy_(
                     torch.as_tensor(np.asarray(state[p + "lower_spline.unnormalized_" + n])))
 
@@ -145,7 +152,7 @@ def state_from_reference_flow(ref_flow) -> Dict[str, np.ndarray]:
                 out[p + f"nn.masks.{i}"] = _np(m).astype(np.float32)
         low = getattr(t, "lower_spline", None)
         if low is not None:
-            for n in ("widths", "heights", "derivatives"):
+            for n in _lower_names(low):
                 out[p + "lower_spline.unnormalized_" + n] = _np(getattr(low, "unnormalized_" + n)).astype(np.float32)
     if not out:
         raise ValueError("no flow layers with .nn.layers / .net found (expected flow.flow_dist.transforms)")

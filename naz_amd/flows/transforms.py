@@ -157,6 +157,14 @@ def _pass_ld_mode(ld_mode, k):
         ops.LD_ROWSUM_ADD if ld_mode == ops.LD_ROWSUM else ld_mode)
 
 
+def _check_order(order):
+    """pyro's two spline orders: "quadratic" (naz's default) and "linear" (a fourth parameter
+    block, the per-bin split position λ; csrc/rls.hip)."""
+    if order not in ("quadratic", "linear"):
+        raise ValueError(f"order must be 'quadratic' or 'linear', got {order!r}")
+    return order
+
+
 def _zeros_rows(x):
     return torch.zeros(x.shape[:-1], device=x.device, dtype=torch.float32)
 
@@ -175,8 +183,9 @@ class _LDCache:
 
 
 class Spline(TransformModule):
-    """[pyro] distributions/transforms/spline.py::Spline (order="quadratic") — elementwise,
-    unconditional; used as SplineCoupling's lower spline.  Parameters are unnormalised."""
+    """[pyro] distributions/transforms/spline.py::Spline — elementwise, unconditional; used as
+    SplineCoupling's lower spline.  Parameters are unnormalised; order="linear" adds pyro's
+    ``unnormalized_lambdas`` (the per-bin split positions, uniform init)."""
 
     domain = constraints.real
     codomain = constraints.real
@@ -184,22 +193,25 @@ class Spline(TransformModule):
 
     def __init__(self, input_dim: int, count_bins: int = 8, bound: float = 3.0, order: str = "quadratic"):
         super().__init__(cache_size=1)
-        if order != "quadratic":
-            raise NotImplementedError("naz_amd: only order='quadratic' (naz's default) is implemented")
-        self.input_dim, self.count_bins, self.bound, self.order = input_dim, count_bins, bound, order
+        self.input_dim, self.count_bins, self.bound, self.order = input_dim, count_bins, bound, _check_order(order)
         self.unnormalized_widths = nn.Parameter(torch.randn(input_dim, count_bins))
         self.unnormalized_heights = nn.Parameter(torch.randn(input_dim, count_bins))
         self.unnormalized_derivatives = nn.Parameter(torch.randn(input_dim, count_bins - 1))
+        if order == "linear":
+            self.unnormalized_lambdas = nn.Parameter(torch.rand(input_dim, count_bins))
         self._cache_log_detJ = None
 
     def flat_raw(self):
-        """[w(S*K) | h(S*K) | d(S*(K-1))] — one broadcast conditioner row (DENSE layout)."""
-        return torch.cat([self.unnormalized_widths.reshape(-1), self.unnormalized_heights.reshape(-1),
-                          self.unnormalized_derivatives.reshape(-1)])
+        """[w(S*K) | h(S*K) | d(S*(K-1))] (| l(S*K) for the linear order) — one broadcast
+        conditioner row (DENSE layout)."""
+        blocks = [self.unnormalized_widths, self.unnormalized_heights, self.unnormalized_derivatives]
+        if self.order == "linear":
+            blocks.append(self.unnormalized_lambdas)
+        return torch.cat([b.reshape(-1) for b in blocks])
 
     def spline_apply(self, x, inverse, ld_mode, ld_out, out=None):
         return ops.rqs(x, self.flat_raw(), self.count_bins, ops.LAYOUT_DENSE, inverse, self.bound, ld_mode, ld_out,
-                       out=out, broadcast_raw=True, fast=True)
+                       out=out, broadcast_raw=True, fast=True, order=self.order)
 
     def _call(self, x):
         y, ld = self.spline_apply(x, False, ops.LD_PERDIM, None)
@@ -222,6 +234,8 @@ def _fused_coupling_layer(m, v, inverse, context, ld_buf, ld_mode):
     the log-det fused, on the module's own one-layer 16-row f16x3 image (re-packed when a parameter
     changes).  None where it does not apply (autograd recording, dropout active, a shape without a
     16-row instantiation, per-dim log-dets): the per-kernel chain runs."""
+    if m.order != "quadratic":  # the fused kernels evaluate the quadratic spline only
+        return None
     if (v.dim() != 2 or ld_mode not in (ops.LD_ROWSUM, ops.LD_ROWSUM_ADD, ops.LD_ROWSUM_SUB) or v.requires_grad
             or (torch.is_grad_enabled() and any(p.requires_grad for p in m.parameters()))):
         return None
@@ -290,7 +304,8 @@ class _ConditionedSplineCoupling(_LDCache, Transform):
         else:
             x1 = v1
         raw = m.nn.raw(x1, self.context)
-        ops.rqs(v2, raw, m.count_bins, ops.LAYOUT_DENSE, inverse, m.bound, ld_mode, ld_buf, out=out[:, s:], fast=True)
+        ops.rqs(v2, raw, m.count_bins, ops.LAYOUT_DENSE, inverse, m.bound, ld_mode, ld_buf, out=out[:, s:], fast=True,
+                order=m.order)
         if not inverse:
             if m.lower_spline is not None:
                 m.lower_spline.spline_apply(v1, False, ld_mode, ld_buf, out=out[:, :s])
@@ -325,11 +340,11 @@ class _ConditionedSplineCoupling(_LDCache, Transform):
         ld_inv = None
         if m.lower_spline is not None:
             x1, ld_inv = ag.rqs(y1, m.lower_spline.flat_raw(), m.count_bins, ops.LAYOUT_DENSE, True, m.bound,
-                                broadcast=True)
+                                broadcast=True, order=m.order)
         else:
             x1 = y1
         raw = m.nn.raw(x1, self.context)
-        x2, ld2 = ag.rqs(y2, raw, m.count_bins, ops.LAYOUT_DENSE, True, m.bound)
+        x2, ld2 = ag.rqs(y2, raw, m.count_bins, ops.LAYOUT_DENSE, True, m.bound, order=m.order)
         ld_inv = ld2 if ld_inv is None else ld_inv + ld2
         return torch.cat([x1, x2], dim=1), -ld_inv
 
@@ -343,10 +358,8 @@ class ConditionalSplineCoupling(ConditionalTransformModule):
     def __init__(self, input_dim: int, split_dim: int, dense_nn: nn.Module, count_bins: int = 8,
                  bound: float = 3.0, order: str = "quadratic", identity: bool = False):
         super().__init__()
-        if order != "quadratic":
-            raise NotImplementedError("naz_amd: only order='quadratic' (naz's default) is implemented")
         self.input_dim, self.split_dim, self.count_bins, self.bound, self.order = (
-            input_dim, split_dim, count_bins, bound, order)
+            input_dim, split_dim, count_bins, bound, _check_order(order))
         self.nn = dense_nn
         self.lower_spline = None if identity else Spline(split_dim, count_bins, bound, order)
 
@@ -389,9 +402,9 @@ class _ConditionedSplineAutoregressive(_LDCache, Transform):
     codomain = constraints.real_vector
     bijective = True
 
-    def __init__(self, arn, context, count_bins, bound):
+    def __init__(self, arn, context, count_bins, bound, order="quadratic"):
         super().__init__(cache_size=1)
-        self.arn, self.context, self.count_bins, self.bound = arn, context, count_bins, bound
+        self.arn, self.context, self.count_bins, self.bound, self.order = arn, context, count_bins, bound, order
         self._cache_log_detJ = None
 
     @property
@@ -404,13 +417,14 @@ class _ConditionedSplineAutoregressive(_LDCache, Transform):
             if y is not None:
                 return y
             raw = self.arn.raw(v, self.context)
-            y, _ = ops.rqs(v, raw, self.count_bins, ops.LAYOUT_ARN, False, self.bound, ld_mode, ld_buf, fast=True)
+            y, _ = ops.rqs(v, raw, self.count_bins, ops.LAYOUT_ARN, False, self.bound, ld_mode, ld_buf, fast=True,
+                           order=self.order)
             return y
         plan = _degree_plan(self.arn, v, ld_mode)
         if plan is not None:
             def step(k, i, raw, x):
                 ops.rqs(v[:, i:i + 1], raw, self.count_bins, ops.LAYOUT_ARN, True, self.bound,
-                        _pass_ld_mode(ld_mode, k), ld_buf, out=x[:, i:i + 1], fast=True)
+                        _pass_ld_mode(ld_mode, k), ld_buf, out=x[:, i:i + 1], fast=True, order=self.order)
             return plan.run(v, self.context, step)
         x = torch.zeros_like(v)
         D = v.shape[-1]
@@ -419,7 +433,8 @@ class _ConditionedSplineAutoregressive(_LDCache, Transform):
             raw = self.arn.raw(x, self.context)
             last = k == D - 1
             x, _ = ops.rqs(v, raw, self.count_bins, ops.LAYOUT_ARN, True, self.bound,
-                           ld_mode if last else ops.LD_ROWSUM, ld_buf if last else scratch, fast=True)
+                           ld_mode if last else ops.LD_ROWSUM, ld_buf if last else scratch, fast=True,
+                           order=self.order)
         return x
 
     def _call(self, x):
@@ -442,19 +457,19 @@ class _ConditionedSplineAutoregressive(_LDCache, Transform):
 
     def _inv_ld(self, y):
         """Differentiable inverse.  Degree-scheduled (every MADE unit once, ARInversePlan.run_grad:
-        per pass the order-k dim's spline on its 3K-1 ARN rows, single-dim naz_rqs_inv + its VJP)
+        per pass the order-k dim's spline on its 3K-1 (linear: 4K-1) ARN rows, single-dim inverse + its VJP)
         unless the conditioner's degree_schedule is off; then pyro's D full passes, autograd running
         back through every pass as pyro's does."""
         plan = self.arn.inverse_plan() if y.dim() == 2 else None
         if plan is not None:
             x, ld = plan.run_grad(y, self.context, lambda k, i, raw: ag.rqs(
-                y[:, i:i + 1], raw, self.count_bins, ops.LAYOUT_ARN, True, self.bound))
+                y[:, i:i + 1], raw, self.count_bins, ops.LAYOUT_ARN, True, self.bound, order=self.order))
             return x, -ld  # the steps' log-dets are the inverse's; the walk wants the forward's
         x = torch.zeros_like(y)
         ld = None
         for _ in range(y.shape[-1]):
             raw = self.arn.raw(x, self.context)
-            x, ld = ag.rqs(y, raw, self.count_bins, ops.LAYOUT_ARN, True, self.bound)
+            x, ld = ag.rqs(y, raw, self.count_bins, ops.LAYOUT_ARN, True, self.bound, order=self.order)
         return x, -ld
 
 
@@ -463,23 +478,19 @@ class ConditionalSplineAutoregressive(ConditionalTransformModule):
 
     def __init__(self, input_dim, autoregressive_nn, count_bins=8, bound=3.0, order="quadratic"):
         super().__init__()
-        if order != "quadratic":
-            raise NotImplementedError("naz_amd: only order='quadratic' (naz's default) is implemented")
-        self.input_dim, self.count_bins, self.bound, self.order = input_dim, count_bins, bound, order
+        self.input_dim, self.count_bins, self.bound, self.order = input_dim, count_bins, bound, _check_order(order)
         self.nn = autoregressive_nn
 
     def condition(self, context):
-        return _ConditionedSplineAutoregressive(self.nn, context, self.count_bins, self.bound)
+        return _ConditionedSplineAutoregressive(self.nn, context, self.count_bins, self.bound, self.order)
 
 
 class SplineAutoregressive(_ConditionedSplineAutoregressive, nn.Module):
     """[pyro] SplineAutoregressive (unconditional)."""
 
     def __init__(self, input_dim, autoregressive_nn, count_bins=8, bound=3.0, order="quadratic"):
-        if order != "quadratic":
-            raise NotImplementedError("naz_amd: only order='quadratic' (naz's default) is implemented")
         Transform.__init__(self, cache_size=1)
-        self.input_dim, self.order = input_dim, order
+        self.input_dim, self.order = input_dim, _check_order(order)
         self.arn_module = autoregressive_nn
         self.context, self.count_bins, self.bound = None, count_bins, bound
         self._cache_log_detJ = None
@@ -710,9 +721,7 @@ def neural_spline_autoregressive(theta_dim, condition_dim, hidden_dim, num_layer
                                  dropout_p=None):
     """naz/flows/transforms.py:165-198."""
     p = _unsupported(use_batchnorm, dropout_p)
-    if order != "quadratic":
-        raise NotImplementedError("naz_amd: only order='quadratic' (naz's default) is implemented")
-    paramdim = [count_bins, count_bins, count_bins - 1]
+    paramdim = [count_bins, count_bins, count_bins - 1] + ([count_bins] if _check_order(order) == "linear" else [])
     transforms, nets = [], []
     for _ in range(num_layers):
         perm = None if random_mask else torch.arange(theta_dim)
@@ -735,14 +744,14 @@ def neural_spline_coupling(theta_dim, condition_dim, hidden_dim, num_layers, cou
                            order="quadratic", activation=nn.Tanh(), use_batchnorm=False, random_perm=False,
                            dropout_p=None, identity=False):
     """naz/flows/transforms.py:201-236 (intent): DenseNN hypernet input cat([ctx, x1]),
-    param_dims [(D-s)K, (D-s)K, (D-s)(K-1)], SplineCoupling per layer.  dropout_p: the
+    param_dims [(D-s)K, (D-s)K, (D-s)(K-1)] (+ [(D-s)K] for order="linear"), SplineCoupling per layer.  dropout_p: the
     ConditionalDenseNNDropout intent (the reference's _forward indexes an undefined
     ``self.dropout_layers[i]``, transforms.py:82): dropout after every hidden activation."""
     p = _unsupported(use_batchnorm, dropout_p)
-    if order != "quadratic":
-        raise NotImplementedError("naz_amd: only order='quadratic' (naz's default) is implemented")
     Dt = theta_dim - split_dim
     param_dims = [Dt * count_bins, Dt * count_bins, Dt * (count_bins - 1)]
+    if _check_order(order) == "linear":
+        param_dims.append(Dt * count_bins)
     transforms, nets = [], []
     for _ in range(num_layers):
         net = (ConditionalDenseNN(split_dim, condition_dim, _hidden(hidden_dim), param_dims=param_dims,

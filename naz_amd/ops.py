@@ -172,20 +172,32 @@ def attach_image(img: Tensor, what: str) -> Tensor:
 
 
 # ----------------------------------------------------------------------------- a1 + a2
+def _spline_params_per_dim(order: str) -> int:
+    """Parameter blocks of K per transformed dim: the raw row is Dt*(n*K - 1) wide."""
+    if order not in ("quadratic", "linear"):
+        raise ValueError(f"order must be 'quadratic' or 'linear', got {order!r}")
+    return 4 if order == "linear" else 3
+
+
 def rqs(x: Tensor, raw: Tensor, count_bins: int, layout: int = LAYOUT_DENSE, inverse: bool = False,
         bound: float = 3.0, ld_mode: int = LD_PERDIM, ld_out: Optional[Tensor] = None,
-        out: Optional[Tensor] = None, broadcast_raw: bool = False, fast: bool = False) -> Tuple[Tensor, Tensor]:
-    """Conditional RQ spline over a conditioner output (naz_rqs_fwd / naz_rqs_inv).
+        out: Optional[Tensor] = None, broadcast_raw: bool = False, fast: bool = False,
+        order: str = "quadratic") -> Tuple[Tensor, Tensor]:
+    """Conditional RQ spline over a conditioner output (naz_rqs_fwd / naz_rqs_inv), or with
+    ``order="linear"`` pyro's rational-linear spline (naz_rls_fwd / naz_rls_inv), whose raw rows
+    carry a fourth block, the per-bin λ: Dt*(4K-1) columns instead of Dt*(3K-1); without ``fast``
+    the linear spline is evaluated in double (the autograd walk's forward).
 
     ``out`` may be a strided 2-D view (unit last stride) to write into; ``broadcast_raw``
     passes a single parameter row (row stride 0) shared by every batch row, which is how
     the unconditional lower spline of a coupling layer runs.  ``fast`` selects the
     select-first hardware-math evaluator (NAZ_RQS_FAST; fp32-grade, HBM-bound) instead of
     the libm-grade one that ``rqs_bwd``'s VJP matches (the autograd walk keeps the latter)."""
+    per_dim = _spline_params_per_dim(order)
     dev = _dev(x, raw, ld_out, out)
     x, ldx = _rows(x)
     B, Dt = x.shape
-    P = Dt * (3 * count_bins - 1)
+    P = Dt * (per_dim * count_bins - 1)
     if broadcast_raw:
         raw = raw.reshape(1, -1).contiguous()
         ldr = 0
@@ -194,14 +206,17 @@ def rqs(x: Tensor, raw: Tensor, count_bins: int, layout: int = LAYOUT_DENSE, inv
     else:
         raw, ldr = _rows(raw)
         if raw.shape != (B, P):
-            raise ValueError(f"raw must be [B, Dt*(3K-1)] = {(B, P)}, got {tuple(raw.shape)}")
+            raise ValueError(f"raw must be [B, Dt*({per_dim}K-1)] = {(B, P)}, got {tuple(raw.shape)}")
     if out is None:
         out = torch.empty_like(x)
     elif out.shape != (B, Dt) or out.stride(1) != 1:
         raise ValueError("out must be a [B, Dt] view with unit last stride")
     if ld_out is None:
         ld_out = torch.empty((B, Dt) if ld_mode == LD_PERDIM else (B,), device=dev, dtype=torch.float32)
-    fn = lib().naz_rqs_inv if inverse else lib().naz_rqs_fwd
+    if order == "linear":
+        fn = lib().naz_rls_inv if inverse else lib().naz_rls_fwd
+    else:
+        fn = lib().naz_rqs_inv if inverse else lib().naz_rqs_fwd
     check(fn(_p(x), ldx, _p(raw), ldr, _p(out), out.stride(0), _p(ld_out), ld_mode, B, Dt, count_bins,
              layout | (RQS_FAST if fast else 0), float(bound), _stream(dev)), "rqs")
     return out, ld_out
@@ -414,20 +429,26 @@ def bounding_inv(y: Tensor, low: Tensor, high: Tensor) -> Tensor:
 # ----------------------------------------------------------------------------- a10 backward
 def rqs_bwd(x: Tensor, raw: Tensor, count_bins: int, layout: int, inverse: bool, bound: float,
             g_out: Optional[Tensor], g_ld: Optional[Tensor], need_g_in: bool = True,
-            broadcast_raw: bool = False) -> Tuple[Optional[Tensor], Tensor]:
-    """VJP of ``rqs`` (naz_rqs_bwd).  ``g_ld``: [B] (gradient of the row-sum ld) or [B, Dt]
-    (per-dim ld) or None.  Returns (g_x or None, g_raw shaped like ``raw``)."""
+            broadcast_raw: bool = False, order: str = "quadratic") -> Tuple[Optional[Tensor], Tensor]:
+    """VJP of ``rqs`` (naz_rqs_bwd; naz_rls_bwd for ``order="linear"``).  ``g_ld``: [B] (gradient
+    of the row-sum ld) or [B, Dt] (per-dim ld) or None.  Returns (g_x or None, g_raw shaped like
+    ``raw``)."""
+    per_dim = _spline_params_per_dim(order)
     dev = _dev(x, raw, g_out, g_ld)
     x, ldx = _rows(x)
     B, Dt = x.shape
-    P = Dt * (3 * count_bins - 1)
+    P = Dt * (per_dim * count_bins - 1)
     if broadcast_raw:
         raw_c = raw.reshape(1, -1).contiguous()
         ldr = 0
+        if raw_c.shape[1] != P:
+            raise ValueError(f"broadcast raw must have {P} entries, got {raw_c.shape[1]}")
         g_raw = torch.zeros(P, device=dev, dtype=torch.float32)
         ldgr = 0
     else:
         raw_c, ldr = _rows(raw)
+        if raw_c.shape != (B, P):
+            raise ValueError(f"raw must be [B, Dt*({per_dim}K-1)] = {(B, P)}, got {tuple(raw_c.shape)}")
         g_raw = torch.empty((B, P), device=dev, dtype=torch.float32)
         ldgr = P
     ldgo = 0
@@ -438,8 +459,9 @@ def rqs_bwd(x: Tensor, raw: Tensor, count_bins: int, layout: int, inverse: bool,
         g_ld = g_ld.contiguous()
         mode = 1 if g_ld.dim() == 1 else 2
     g_in = torch.empty((B, Dt), device=dev, dtype=torch.float32) if need_g_in else None
-    check(lib().naz_rqs_bwd(int(inverse), _p(x), ldx, _p(raw_c), ldr, _p(g_out), ldgo, _p(g_ld), mode, _p(g_in), Dt,
-                            _p(g_raw), ldgr, B, Dt, count_bins, layout, float(bound), _stream(dev)), "rqs_bwd")
+    fn = lib().naz_rls_bwd if order == "linear" else lib().naz_rqs_bwd
+    check(fn(int(inverse), _p(x), ldx, _p(raw_c), ldr, _p(g_out), ldgo, _p(g_ld), mode, _p(g_in), Dt,
+             _p(g_raw), ldgr, B, Dt, count_bins, layout, float(bound), _stream(dev)), "rqs_bwd")
     return g_in, (g_raw.reshape(raw.shape) if broadcast_raw else g_raw)
 
 
