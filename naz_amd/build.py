@@ -22,13 +22,10 @@ ARCH = os.environ.get("NAZ_OFFLOAD_ARCH", "gfx950")
 # Per-source flags.  The MFMA kernels are built without the SLP vectorizer: the packed f32 VALU
 # ops it forms (v_pk_add/mul/fma_f32) issue slower than scalar ones beside MFMAs, and the
 # packing moves add register pressure (spills in coupling_x6_kernel with it on).
-SOURCE_FLAGS = {"coupling.hip": ["-fno-slp-vectorize"], "cnf.hip": ["-fno-slp-vectorize"],
-                "made.hip": ["-fno-slp-vectorize"]}
-SOURCES = ["rqs.hip", "rls.hip", "dense.hip", "gemm.hip", "gemm_rows.hip", "elementwise.hip", "made.hip", "coupling.hip", "cnf.hip", "capi.cpp"]
-# sources compiled more than once with a part macro (object name suffix, extra flags): coupling.hip
-# holds the coupling, the autoregressive and the autoregressive-backward kernels, ~5 min of device
-# compile in one object
-PARTS = {"coupling.hip": [("", ["-DNAZ_PART=1"]), ("_ar", ["-DNAZ_PART=2"]), ("_arb", ["-DNAZ_PART=3"])]}
+SOURCE_FLAGS = {s: ["-fno-slp-vectorize"]
+                for s in ("coupling.hip", "made_ar.hip", "made_ar_bwd.hip", "cnf.hip", "made.hip")}
+SOURCES = ["rqs.hip", "rls.hip", "dense.hip", "gemm.hip", "gemm_rows.hip", "elementwise.hip", "made.hip",
+           "coupling.hip", "made_ar.hip", "made_ar_bwd.hip", "cnf.hip", "capi.cpp"]
 
 
 def hipcc() -> str:
@@ -48,7 +45,6 @@ def _compile(src: Path, obj: Path, extra: list) -> str:
            f"-I{INCLUDE}", "-c", str(src), "-o", str(obj)] + SOURCE_FLAGS.get(src.name, []) + extra
     if src.suffix == ".cpp":
         cmd[1:2] = []  # host-only TU
-        cmd += ["-x", "c++"] if False else []
     started = time.time()
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -61,7 +57,7 @@ def _compile(src: Path, obj: Path, extra: list) -> str:
 
 
 def build(verbose: bool = False, jobs: int = 4, extra: list | None = None, variant: str | None = None) -> Path:
-    """Build the library.  `variant` (with `extra` flags, e.g. ablation -D's) builds
+    """Build the library.  `variant` (with `extra` compiler flags) builds
     naz_amd/lib/libnazhip_<variant>.so from objects in naz_amd/build/<variant>/ instead."""
     extra = list(extra or [])
     obj_dir = OBJ / variant if variant else OBJ
@@ -71,15 +67,12 @@ def build(verbose: bool = False, jobs: int = 4, extra: list | None = None, varia
     hm = _headers_mtime()
     todo = []
     objs = []
-    for s in SOURCES:
-        src = CSRC / s
-        for suffix, flags in PARTS.get(s, [("", [])]):
-            obj = obj_dir / (src.stem + suffix + ".o")
-            objs.append(obj)
-            if not obj.exists() or obj.stat().st_mtime < max(src.stat().st_mtime, hm):
-                todo.append((src, obj, flags))
+    for src, obj in zip((CSRC / s for s in SOURCES), _objects(obj_dir)):
+        objs.append(obj)
+        if not obj.exists() or obj.stat().st_mtime < max(src.stat().st_mtime, hm):
+            todo.append((src, obj))
     with cf.ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
-        for (src, obj, _), warn in zip(todo, ex.map(lambda t: _compile(t[0], t[1], extra + t[2]), todo)):
+        for (src, obj), warn in zip(todo, ex.map(lambda t: _compile(t[0], t[1], extra), todo)):
             if verbose:
                 print(f"[naz_amd.build] {src.name} -> {obj.name}", file=sys.stderr)
                 if warn.strip():
@@ -98,15 +91,15 @@ DEBUG_LIB = LIB.with_name("libnazhip_debug.so")
 def build_debug(verbose: bool = False) -> Path:
     """naz_amd/lib/libnazhip_debug.so: the library with the fused coupling kernels built with
     -DNAZ_DEBUG_NONFINITE (the first non-finite row state recorded as (workgroup, layer, stage,
-    row), naz_debug_nonfinite).  Only coupling.hip's part 1 reads the flag, so the other objects
-    are the default build's (built first if needed)."""
+    row), naz_debug_nonfinite).  Only coupling.hip reads the flag, so the other objects are the
+    default build's (built first if needed)."""
     build(verbose=verbose)
     obj_dir = OBJ / "debug"
     obj_dir.mkdir(parents=True, exist_ok=True)
     src = CSRC / "coupling.hip"
     dobj = obj_dir / "coupling.o"
     if not dobj.exists() or dobj.stat().st_mtime < max(src.stat().st_mtime, _headers_mtime()):
-        _compile(src, dobj, ["-DNAZ_DEBUG_NONFINITE", "-DNAZ_PART=1"])
+        _compile(src, dobj, ["-DNAZ_DEBUG_NONFINITE"])
         if verbose:
             print(f"[naz_amd.build] coupling.hip -> debug/{dobj.name}", file=sys.stderr)
     objs = [dobj if o.name == "coupling.o" else o for o in _objects(OBJ)]
@@ -119,7 +112,7 @@ def build_debug(verbose: bool = False) -> Path:
 
 
 def _objects(obj_dir: Path) -> list:
-    return [obj_dir / (CSRC.joinpath(s).stem + suffix + ".o") for s in SOURCES for suffix, _ in PARTS.get(s, [("", [])])]
+    return [obj_dir / (Path(s).stem + ".o") for s in SOURCES]
 
 
 if __name__ == "__main__":

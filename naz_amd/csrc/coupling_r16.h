@@ -1,5 +1,4 @@
-// 16-row-wave variant of the fused coupling flow (NAZ_MFMA_F16X3_R16; included by coupling.hip,
-// which supplies split8_f16, f16_piece_bits, sig_fold, kSigScale, stage_issue, kChunk, ...).
+// 16-row-wave variant of the fused coupling flow (NAZ_MFMA_F16X3_R16).
 //
 // Why: the 32-row x6 kernel keeps each activation block in a 32x32 accumulator (16 VGPRs per
 // feature block) and needs ~250 VGPRs, i.e. two waves per SIMD; PMC shows ~28 % of its cycles
@@ -25,6 +24,8 @@
 // a second stage-A image of the same size).  Activation fold, select-first spline and LDS-DMA
 // ring as in coupling_x6_kernel.
 #pragma once
+#include "../../include/naz_hip.h"  // NAZ_LD_ROWSUM*
+#include "coupling_x6.h"
 
 namespace naz {
 
@@ -42,19 +43,24 @@ NAZ_DEV floatx4 mfma3_16(const Frag2& a, const Frag2& b, floatx4 acc) {
 
 // GEMM stages run at wave priority 1, the splines at 0: a SIMD's matrix pipe is fed first
 // and the spline VALU of the other waves fills the MFMA issue gaps (+0.5 %, same-box A/B).
-// NAZ_R16_STATIC_PRIO (experiment): no per-stage flips; the second-dispatched half of the workgroup
-// (waves 4-7, the arbitration losers) runs at priority 1 for the whole kernel (MI355X_MICROARCH.md,
-// "two waves per SIMD" item 4).
-#if defined(NAZ_R16_NO_PRIO) || defined(NAZ_R16_STATIC_PRIO)
-#define R16_PRIO(p) ((void)0)
-#else
-#define R16_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#endif
+// Static priority (no per-stage flips; waves 4-7, the second-dispatched half of the workgroup,
+// at priority 1 for the whole kernel): no gain, same-box A/B.
 
-#ifndef NAZ_R16_WAVES
-#define NAZ_R16_WAVES 8
-#endif
-constexpr int kR16Waves = NAZ_R16_WAVES;     // 8 waves x 16 rows = 128 rows per workgroup
+// NAZ_DEBUG_NONFINITE builds (python -m naz_amd.build debug): the fused log_prob kernel records the
+// FIRST non-finite row state as {1, workgroup, layer, stage counter, row} (naz_debug_nonfinite
+// reads and clears it).  The record exists in every build (coupling.hip defines it); only the
+// debug build writes it.
+extern __device__ int64_t g_nonfinite[5];
+NAZ_DEV void debug_nonfinite_probe(bool bad, int64_t row, int layer, int stage) {
+  if (bad && atomicCAS(reinterpret_cast<unsigned long long*>(&g_nonfinite[0]), 0ull, 1ull) == 0ull) {
+    g_nonfinite[1] = blockIdx.x;
+    g_nonfinite[2] = layer;
+    g_nonfinite[3] = stage;
+    g_nonfinite[4] = row;
+  }
+}
+
+constexpr int kR16Waves = 8;                 // 8 waves x 16 rows = 128 rows per workgroup
 constexpr int kR16Rows = 16 * kR16Waves;
 
 // feature carried by k-slot 8q + j of 32-k step t (GEMM2/3 inputs)
@@ -82,11 +88,7 @@ struct CfgR16 {
   // GEMM3 in two halves of NO/2 output blocks (SPLIT3, two upper dims per quarter): half 0 holds
   // every parameter of dim 0, so dim 0's spline can run beside half 1's MFMAs, and half 1 reuses
   // half 0's B fragments instead of the GEMM2 accumulators
-#ifdef NAZ_R16_NOSPLIT3
-  static constexpr bool SPLIT3 = false;
-#else
   static constexpr bool SPLIT3 = DQ == 2 && NO % 2 == 0 && (P + 3) / 4 <= NO / 2;
-#endif
   static constexpr int NOC = SPLIT3 ? NO / 2 : NO;     // output blocks per GEMM3 stage
   static constexpr int KB3 = pick_kb(NOC, 16 * NO), NB3H = KS2 / KB3, NB3 = (SPLIT3 ? 2 : 1) * NB3H;
   // stage A (fp16 image; the fp32 image A32 has the same size and bias/table offsets):
@@ -238,7 +240,7 @@ __global__ void coupling_pack_r16_kernel(const float* __restrict__ flat, float* 
 }
 
 // acc[o] += A(o, t) · B(t) over k-steps [0, KB), t outer, o inner, with each A fragment read one
-// MFMA triple ahead (untracked LDS reads with counted waits, coupling.hip lds_read_b128_untracked):
+// MFMA triple ahead (untracked LDS reads with counted waits, lds_ring.h lds_read_b128_untracked):
 // for kernels with too few waves per SIMD to hide an LDS read behind other waves' work (the
 // training backward: two).  bfn(t) returns k-step t's B fragment (formed inside the loop, so the
 // lazy forms' activation VALU still lands between MFMAs).
@@ -276,10 +278,6 @@ NAZ_DEV void gemm_r16_pf(floatx4 (&acc)[NB], const float* __restrict__ stage, in
 // acc[o] += A(o, t) · B(t) over k-steps [0, KB) with B fragments given (PF: gemm_r16_pf)
 template <int NB, int KB, bool PF = false>
 NAZ_DEV void gemm_r16_stage(floatx4 (&acc)[NB], const float* __restrict__ stage, int lane, const Frag2 (&bf)[KB]) {
-#ifdef NAZ_ABL_NOGEMM
-  for (int o = 0; o < NB; ++o) acc[o][0] += (float)bf[0].h[0] * 1e-30f;
-  return;
-#endif
   if constexpr (PF) {
     gemm_r16_pf<NB, KB>(acc, stage, lane, [&](auto tc) -> Frag2 { return bf[decltype(tc)::value]; });
     return;
@@ -325,10 +323,6 @@ NAZ_DEV void gemm_r16_lazy(floatx4 (&acc)[NB], const float* __restrict__ stage, 
       if constexpr (ACT) v[j] = sig_fold(v[j]);
     }
     const Frag2 b = split8_f16(v);
-#ifdef NAZ_ABL_NOGEMM
-    for (int o = 0; o < NB; ++o) acc[o][0] += (float)b.h[0] * 1e-30f;
-    continue;
-#endif
 #pragma unroll
     for (int o = 0; o < NB; ++o) {
       const int base = ((o * KB + t) * 2) * 64 + lane;
@@ -366,10 +360,6 @@ NAZ_DEV void gemm3_stage(floatx4 (&acc)[CF::NO], const float* __restrict__ cur, 
       }
       f3[T0 + t] = split8_f16(v);
     }
-#ifdef NAZ_ABL_NOGEMM
-    for (int o = 0; o < CF::NOC; ++o) acc[OB + o][0] += (float)f3[T0 + t].h[0] * 1e-30f;
-    continue;
-#endif
 #pragma unroll
     for (int o = 0; o < CF::NOC; ++o) {
       const int base = ((o * CF::KB3 + t) * 2) * 64 + lane;
@@ -379,32 +369,14 @@ NAZ_DEV void gemm3_stage(floatx4 (&acc)[CF::NO], const float* __restrict__ cur, 
   }
 }
 
-// Training forward (VAR = 1, coupling_train.h): the log_prob walk of the NLL step with the
-// reference walk's libm-grade activation and spline (tanh_f / build_tables + rqs_apply, not
-// the hardware-transcendental fold and select-first spline) and every layer's input state
-// written to states[l + 1][row][:] (states[0] = z), for the backward kernel to recompute from.
-// The GEMMs keep the f16x3 split.  Activated values are -tanh/2 (the fold's convention), so the
-// packed image is the same.
-constexpr float kInvSigScale = 0.34657359027997264f;  // 1 / kSigScale = ln 2 / 2
-// Training kernels' math: by default the fused inference kernel's own (sigmoid-fold activation,
+// Training forward (VAR = 1, coupling_train.h): the log_prob walk of the NLL step with every
+// layer's input state written to states[l + 1][row][:] (states[0] = z), for the backward kernel
+// to recompute from.  Its math is the fused inference kernel's own (sigmoid-fold activation,
 // select-first spline on hardware transcendentals, table lower spline), so the NLL step's loss is
-// the log_prob the metric kernel computes.  NAZ_TRAIN_ACCURATE: libm-grade tanh and spline.
-#ifdef NAZ_TRAIN_ACCURATE
-constexpr bool kTrainFast = false;
-#else
-constexpr bool kTrainFast = true;
-#endif
-NAZ_DEV float acc_fold(float v) { return -0.5f * tanh_f<kTrainFast>(v * kInvSigScale); }
-
-// waves per SIMD: the training forward (VAR = 1) as inference, 4 (128 VGPRs, 12 B of scratch at
-// config 3); NAZ_R16_TRAIN_W2: 2, the round-2 form (A/B)
-#ifdef NAZ_R16_TRAIN_W2
-#define NAZ_R16_TRAIN_WAVES_PER_SIMD_SEL(VAR) ((VAR) == 0 ? 4 : 2)
-#else
-#define NAZ_R16_TRAIN_WAVES_PER_SIMD_SEL(VAR) 4
-#endif
+// the log_prob the metric kernel computes.
+// Waves per SIMD: 4 for every VAR (128 VGPRs, 12 B of scratch in the training forward at config 3).
 template <class CF, bool DIR_INV, int VAR = 0>
-__global__ void __launch_bounds__(kR16Rows * 4, NAZ_R16_TRAIN_WAVES_PER_SIMD_SEL(VAR)) coupling_r16_kernel(
+__global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
     const float* __restrict__ packed, int L, const float* __restrict__ x, int64_t ldx,
     const float* __restrict__ ctx, int64_t ldc, const float* __restrict__ low, const float* __restrict__ high,
     float* __restrict__ out_lp, float* __restrict__ yout, int64_t ldy, int64_t B, float bound,
@@ -420,9 +392,6 @@ __global__ void __launch_bounds__(kR16Rows * 4, NAZ_R16_TRAIN_WAVES_PER_SIMD_SEL
   const int64_t row = (int64_t)blockIdx.x * kR16Rows + wave * 16 + (lane & 15);
   const bool valid = row < B;
   const int64_t crow = valid ? row : 0;
-#ifdef NAZ_R16_STATIC_PRIO
-  if (wave >= kR16Waves / 2) __builtin_amdgcn_s_setprio(1);
-#endif
 
   float zl[CF::SQ], zu[CF::DQ];
   float ldsum = 0.f, logjac = 0.f;
@@ -473,7 +442,7 @@ __global__ void __launch_bounds__(kR16Rows * 4, NAZ_R16_TRAIN_WAVES_PER_SIMD_SEL
   const bool g1f16 = ok;
   const int a_off = g1f16 ? 0 : CF::A32_OFF;
 
-  const RingSrc ring(packed, (int64_t)L * CF::LAYER);
+  const RingSrc ring{packed};
   stage_issue<CF::A_SIZE, kR16Waves>(slot0, ring, (DIR_INV ? (L - 1) : 0) * CF::LAYER + a_off);
 
   const RqsConsts<CF::K, DIR_INV> rc(bound);
@@ -523,31 +492,13 @@ __global__ void __launch_bounds__(kR16Rows * 4, NAZ_R16_TRAIN_WAVES_PER_SIMD_SEL
         ud[k] = acc3[(b0 + k) >> 2][(b0 + k) & 3];
       }
       float ld;
-#ifdef NAZ_ABL_NOSPLINE
-      if constexpr (VAR == 0) {
-        float sacc = 0.f;
-#pragma unroll
-        for (int k = 0; k < CF::K; ++k) sacc += uw[k] + uh[k];
-        zu[u] += 1e-30f * sacc;
-        return;
-      }
-#endif
-      if constexpr (VAR == 1 && !kTrainFast) {
-        SplineTables<CF::K> tb;
-        build_tables<CF::K, kTrainFast>(uw, uh, ud, bound, tb);
-        zu[u] = rqs_apply<CF::K, DIR_INV, kTrainFast>(tb, zu[u], bound, ld);
-        ldsum += DIR_INV ? -ld : ld;
-      } else {
-        zu[u] = rqs_select<CF::K, DIR_INV>(uw, uh, ud, zu[u], bound, rc, ld);
-        ldsum += DIR_INV ? -ld : ld;
-      }
+      zu[u] = rqs_select<CF::K, DIR_INV>(uw, uh, ud, zu[u], bound, rc, ld);
+      ldsum += DIR_INV ? -ld : ld;
     };
 
     static_for<0, CF::NSTG>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-#ifndef NAZ_ABL_NOBARRIER
       ring_barrier();  // stage j has landed in slot (g&1); every wave is done with the other slot
-#endif
       const float* cur = (g & 1) ? slot1 : slot0;
       float* nxt = (g & 1) ? slot0 : slot1;
       if constexpr (j + 1 < CF::NSTG) {
@@ -561,27 +512,10 @@ __global__ void __launch_bounds__(kR16Rows * 4, NAZ_R16_TRAIN_WAVES_PER_SIMD_SEL
         // ---------------- stage A: lower spline (inverse), GEMM1 over [ctx | x1]
 #pragma unroll
         for (int u = 0; u < CF::SQ; ++u) {
-#ifdef NAZ_ABL_NOLOWER
-          if constexpr (false) {
-#else
           if constexpr (DIR_INV && CF::LOWER) {
-#endif
             float ld;
-            if constexpr (VAR == 1 && !kTrainFast) {
-              SplineTables<CF::K> tb;
-              const float* tp = cur + CF::A_TBL + (q * CF::SQ + u) * CF::TBL;
-#pragma unroll
-              for (int k = 0; k <= CF::K; ++k) {
-                tb.cw[k] = tp[k];
-                tb.ch[k] = tp[CF::K + 1 + k];
-                tb.dv[k] = tp[2 * (CF::K + 1) + k];
-              }
-              zl[u] = rqs_apply<CF::K, true, kTrainFast>(tb, zl[u], bound, ld);
-              ldsum -= ld;  // ldsum carries the forward maps' log-dets (rqs_apply: the inverse's)
-            } else {
-              zl[u] = rqs_table<CF::K, true>(cur + CF::A_TBL + (q * CF::SQ + u) * CF::TBL, zl[u], bound, ld);
-              ldsum -= ld;
-            }
+            zl[u] = rqs_table<CF::K, true>(cur + CF::A_TBL + (q * CF::SQ + u) * CF::TBL, zl[u], bound, ld);
+            ldsum -= ld;  // ldsum carries the forward maps' log-dets (rqs_table: the inverse's)
           }
         }
         float in[CF::KS1 * 8];
@@ -603,11 +537,7 @@ __global__ void __launch_bounds__(kR16Rows * 4, NAZ_R16_TRAIN_WAVES_PER_SIMD_SEL
             acc1[o] = floatx4{bv.x, bv.y, bv.z, bv.w};
           }
         }
-#ifdef NAZ_R16_NO_F32_G1
-        if (true) {
-#else
         if (g1f16) {
-#endif
           Frag2 bf[CF::KS1];
 #pragma unroll
           for (int t = 0; t < CF::KS1; ++t) {
@@ -616,9 +546,9 @@ __global__ void __launch_bounds__(kR16Rows * 4, NAZ_R16_TRAIN_WAVES_PER_SIMD_SEL
             for (int jj = 0; jj < 8; ++jj) v[jj] = in[8 * t + jj];
             bf[t] = split8_f16(v);
           }
-          R16_PRIO(1);
+          __builtin_amdgcn_s_setprio(1);
           gemm_r16_stage<CF::HB, CF::KS1>(acc1, cur, lane, bf);
-          R16_PRIO(0);
+          __builtin_amdgcn_s_setprio(0);
         } else {
           // exact fp32: 8 KS1 k-steps of 4; k-step s on this lane = slot (s / 8, s % 8)
           const float4* p4 = reinterpret_cast<const float4*>(cur);
@@ -644,25 +574,6 @@ __global__ void __launch_bounds__(kR16Rows * 4, NAZ_R16_TRAIN_WAVES_PER_SIMD_SEL
       } else if constexpr (j <= CF::NB2) {
         // ---------------- stage B_s: GEMM2 k-steps [T0, T0 + KB2)
         constexpr int s = j - 1, T0 = s * CF::KB2;
-#ifdef NAZ_R16_EAGER_ACT
-#pragma unroll
-        for (int b = 2 * T0; b < 2 * (T0 + CF::KB2); ++b)  // activate the blocks these k-steps read
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc1[b][r] = sig_fold(acc1[b][r]);
-        constexpr bool kLazyAct = false;
-#else
-#ifdef NAZ_ABL_NOTANH
-        constexpr bool kLazyAct = false, kNoAct = true;
-#else
-        constexpr bool kLazyAct = VAR == 0 || kTrainFast, kNoAct = false;  // activated per k-step inside gemm_r16_lazy
-#endif
-        if constexpr (!kLazyAct && !kNoAct) {
-#pragma unroll
-          for (int b = 2 * T0; b < 2 * (T0 + CF::KB2); ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc1[b][r] = acc_fold(acc1[b][r]);
-        }
-#endif
         if constexpr (s == 0) {
           const float4* b4 = reinterpret_cast<const float4*>(cur + CF::B_BIAS);
 #pragma unroll
@@ -671,29 +582,18 @@ __global__ void __launch_bounds__(kR16Rows * 4, NAZ_R16_TRAIN_WAVES_PER_SIMD_SEL
             acc2[o] = floatx4{bv.x, bv.y, bv.z, bv.w};
           }
         }
-        R16_PRIO(1);
-        gemm_r16_lazy<CF::HB, CF::KB2, T0, kLazyAct>(acc2, cur, lane, acc1);
-        R16_PRIO(0);
+        __builtin_amdgcn_s_setprio(1);
+        gemm_r16_lazy<CF::HB, CF::KB2, T0, true>(acc2, cur, lane, acc1);  // activated per k-step inside
+        __builtin_amdgcn_s_setprio(0);
       } else {
         // ---------------- stage C_s: GEMM3 (two halves of output blocks when SPLIT3)
-        constexpr int s = j - 1 - CF::NB2, T0s = (s % CF::NB3H) * CF::KB3;
-#ifdef NAZ_ABL_NOTANH
-        constexpr bool kLazyAct = false, kNoAct = true;
-#else
-        constexpr bool kLazyAct = VAR == 0 || kTrainFast, kNoAct = false;
-#endif
-        if constexpr (!kLazyAct && !kNoAct && s < CF::NB3H) {  // accurate training forward: eager
-#pragma unroll
-          for (int b = 2 * T0s; b < 2 * (T0s + CF::KB3); ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc2[b][r] = acc_fold(acc2[b][r]);
-        }
+        constexpr int s = j - 1 - CF::NB2;
         constexpr bool kHost = CF::SPLIT3 && s == CF::NB3H;  // first stage of half 1: dim 0's spline
-        if constexpr (!kHost) R16_PRIO(1);
-        gemm3_stage<CF, s, kLazyAct>(acc3, cur, lane, q, acc2, f3);
-        if constexpr (!kHost) R16_PRIO(0);
+        if constexpr (!kHost) __builtin_amdgcn_s_setprio(1);
+        gemm3_stage<CF, s, true>(acc3, cur, lane, q, acc2, f3);
+        if constexpr (!kHost) __builtin_amdgcn_s_setprio(0);
         // dim 0's spline in the stage that issues half 1's MFMAs (the compiler still issues the
-        // MFMAs first: measured the same as NAZ_R16_NOSPLIT3, also with sched_group_barrier pins)
+        // MFMAs first: measured the same as without SPLIT3, also with sched_group_barrier pins)
         if constexpr (kHost) upper(std::integral_constant<int, 0>{});
       }
     });

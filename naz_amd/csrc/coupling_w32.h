@@ -1,5 +1,5 @@
-// 32-row-wave fused coupling flow on v_mfma_f32_32x32x16_f16 (NAZ_MFMA_F16X3; included by
-// coupling.hip after the x6 kernel, whose packed image — CfgX6<..., P23 = 2> — it reads).
+// 32-row-wave fused coupling flow on v_mfma_f32_32x32x16_f16 (NAZ_MFMA_F16X3), over the
+// x6 kernel's packed image, CfgX6<..., P23 = 2>.
 //
 // Why (round 4): the 16-row r16 kernel is bound by its SIMDs' VECTOR-ISSUE port, not by the matrix
 // pipe.  Its PMC (profiles/pmc_r03_headline.json) puts SQ_ACTIVE_INST_VALU (one quad-cycle per VALU
@@ -22,6 +22,7 @@
 // Precision: f16x3 (the x6 image's f16 pieces); GEMM1 runs the exact-split bf16x6 image for a
 // workgroup whose context or data values reach 2^15 (as the x6 kernel).
 #pragma once
+#include "coupling_x6.h"
 
 namespace naz {
 
@@ -29,7 +30,6 @@ namespace naz {
 // values are activated and split right before its MFMAs)
 template <int NB, int KB, int T0, int NX>
 NAZ_DEV void gemm_w32_lazy(floatx16 (&acc)[NB], const float* __restrict__ stage, int lane, floatx16 (&x)[NX]) {
-#ifndef NAZ_W32_NO_PREFETCH
   // the A fragments one MFMA triple ahead, read untracked with a counted wait (lds_wait<2>: the
   // next triple's two reads may stay in flight), 8 more VGPRs (244 of 256)
   const unsigned base = (unsigned)(uintptr_t)to_lds(stage) + 16u * lane;
@@ -43,7 +43,7 @@ NAZ_DEV void gemm_w32_lazy(floatx16 (&acc)[NB], const float* __restrict__ stage,
     constexpr int t = decltype(tc)::value;
     float v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = NAZ_TANH(x[(T0 + t) >> 1][8 * ((T0 + t) & 1) + j]);
+    for (int j = 0; j < 8; ++j) v[j] = sig_fold(x[(T0 + t) >> 1][8 * ((T0 + t) & 1) + j]);
     const Frag2 b = split8_f16(v);
     static_for<0, NB>([&](auto oc) {
       constexpr int o = decltype(oc)::value;
@@ -61,22 +61,6 @@ NAZ_DEV void gemm_w32_lazy(floatx16 (&acc)[NB], const float* __restrict__ stage,
       acc[o] = mfma3(a, b, acc[o]);
     });
   });
-#else
-  const u32x4* c4 = reinterpret_cast<const u32x4*>(stage);
-#pragma unroll
-  for (int t = 0; t < KB; ++t) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = NAZ_TANH(x[(T0 + t) >> 1][8 * ((T0 + t) & 1) + j]);
-    const Frag2 b = split8_f16(v);
-#pragma unroll
-    for (int o = 0; o < NB; ++o) {
-      const int base = ((o * KB + t) * 2) * 64 + lane;
-      const Frag2 a{__builtin_bit_cast(half8, c4[base]), __builtin_bit_cast(half8, c4[base + 64])};
-      acc[o] = mfma3(a, b, acc[o]);
-    }
-  }
-#endif
 }
 
 template <class CF, bool DIR_INV>
@@ -186,13 +170,11 @@ __global__ void __launch_bounds__(kX6Rows * 2, kX6Waves / 2) coupling_w32_kernel
         // ---------------- stage A: lower spline (inverse), GEMM1 over [ctx | x1]
 #pragma unroll
         for (int q = 0; q < CF::SH; ++q) {
-#ifndef NAZ_ABL_NOLOWER
           if constexpr (DIR_INV && CF::LOWER) {
             float ld;
             zl[q] = rqs_table<CF::K, true>(cur + CF::A_TBL + (h * CF::SH + q) * CF::TBL, zl[q], bound, ld);
             ldsum -= ld;
           }
-#endif
         }
         init_bias<CF::HB>(acc1, cur + CF::A_BIAS, h);
         if (g1f16) {
@@ -208,7 +190,7 @@ __global__ void __launch_bounds__(kX6Rows * 2, kX6Waves / 2) coupling_w32_kernel
             xf[t] = split8_f16(v);
           }
           const u32x4* c4 = reinterpret_cast<const u32x4*>(cur);
-          R16_PRIO(1);
+          __builtin_amdgcn_s_setprio(1);
 #pragma unroll
           for (int t = 0; t < CF::KS0; ++t)
 #pragma unroll
@@ -217,7 +199,7 @@ __global__ void __launch_bounds__(kX6Rows * 2, kX6Waves / 2) coupling_w32_kernel
               const Frag2 a{__builtin_bit_cast(half8, c4[base]), __builtin_bit_cast(half8, c4[base + 64])};
               acc1[o] = mfma3(a, t < CF::CT ? cfr[t < CF::CT ? t : 0] : xf[t >= CF::CT ? t - CF::CT : 0], acc1[o]);
             }
-          R16_PRIO(0);
+          __builtin_amdgcn_s_setprio(0);
         } else {
           // exact-split bf16x6 GEMM1 (the x6 image at offset 0; the context reloaded: a rare path)
           Frag3 bf[CF::KS0];
@@ -250,16 +232,16 @@ __global__ void __launch_bounds__(kX6Rows * 2, kX6Waves / 2) coupling_w32_kernel
         // ---------------- stage B_s: GEMM2 k-steps [T0, T0 + KB2), activation per k-step
         constexpr int s = j - 1, T0 = s * CF::KB2;
         if constexpr (s == 0) init_bias<CF::HB>(acc2, cur + CF::B_BIAS, h);
-        R16_PRIO(1);
+        __builtin_amdgcn_s_setprio(1);
         gemm_w32_lazy<CF::HB, CF::KB2, T0>(acc2, cur, lane, acc1);
-        R16_PRIO(0);
+        __builtin_amdgcn_s_setprio(0);
       } else {
         // ---------------- stage C_s: GEMM3 k-steps [T0, T0 + KB3) -> raw spline parameters
         constexpr int s = j - 1 - CF::NB2, T0 = s * CF::KB3;
         if constexpr (s == 0) init_bias<CF::NO>(acc3, cur + CF::C_BIAS, h);
-        R16_PRIO(1);
+        __builtin_amdgcn_s_setprio(1);
         gemm_w32_lazy<CF::NO, CF::KB3, T0>(acc3, cur, lane, acc2);
-        R16_PRIO(0);
+        __builtin_amdgcn_s_setprio(0);
       }
     });
 
@@ -278,16 +260,9 @@ __global__ void __launch_bounds__(kX6Rows * 2, kX6Waves / 2) coupling_w32_kernel
         const int sd = q * CF::P + 2 * CF::K + k;
         ud[k] = acc3[sd >> 4][sd & 15];
       }
-#ifdef NAZ_ABL_NOSPLINE
-      float sacc = 0.f;
-#pragma unroll
-      for (int k = 0; k < CF::K; ++k) sacc += uw[k] + uh[k];
-      zu[q] += 1e-30f * sacc;
-#else
       float ld;
       zu[q] = rqs_select<CF::K, DIR_INV>(uw, uh, ud, zu[q], bound, rc, ld);
       ldsum += DIR_INV ? -ld : ld;
-#endif
     }
   }
 

@@ -2,8 +2,6 @@
 // L = Σ_rows g_lp · log p(x | ctx) for the NUTS / HMC potential of naz's Bayesian MAF
 // (bflow_jax_maf.py:231-235: jax.grad of flow_lp(unravel(p)).sum(); hmc_maf_exact.py:118-133) and
 // the maf NLL step (train_flows.py:194-213).  SURVEY.md §8f rank 1 over §8a a5/a6.
-// Included by coupling.hip (part 3) after made_ar_r16.h (CfgAR, CfgARF, split8_f16, sig_fold,
-// stage_issue, ring_barrier, bwd_row_scale, ...).
 //
 // The forward is the fused inverse kernel (made_ar_r16_kernel) with its per-layer outputs saved:
 // states[l] = s_l, the output of layer l's inverse (layer l maps s_{l+1} -> s_l; s_0 = z).
@@ -33,6 +31,8 @@
 // the backward images order Wᵀ's columns to match, so every chain step lands in the forward's
 // activation layout with no shuffles.
 #pragma once
+#include "coupling_train.h"  // bwd_row_scale
+#include "made_ar_r16.h"
 
 namespace naz {
 
@@ -70,11 +70,7 @@ struct CfgARB {
     return y;
   }
   static constexpr T0Tab T0T = make_t0();
-#ifdef NAZ_AR_BWD_DENSE_K  // (A/B: every k-step)
-  static constexpr int kt0(int) { return 0; }
-#else
   static constexpr int kt0(int j) { return j >= 1 && j < NUB - 1 ? T0T.t0[hid_b(j)] : 0; }
-#endif
   static constexpr int unit_floats(int j) { return j == 0 ? (TBLF + 255) / 256 * 256 : (KSH - kt0(j)) * OT; }
   struct Layout {
     int sid[NUB], off[NUB], sfl[NUB];

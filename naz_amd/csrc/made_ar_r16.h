@@ -3,8 +3,6 @@
 // ConditionalAutoRegressiveNN with NHID tanh hidden layers) in ONE launch.  SURVEY.md §8a rows
 // a4/a5/a6/a8 (naz/flows/transforms.py:133-198, pyro SplineAutoregressive._inverse /
 // AffineAutoregressive._inverse); the §8b `naz_spline_ar_inv` / `naz_affine_ar_inv` entries.
-// Included by coupling.hip after coupling_r16.h (Frag2, split8_f16, sig_fold, kSigScale,
-// stage_issue, r16_feat, ...).
 //
 // The reference inverts a layer with D sequential passes of the WHOLE MADE network (pass k makes
 // the dim of order k final).  A hidden unit with mask index m ("degree": it reads the context and
@@ -30,6 +28,7 @@
 // (nsa at H = 128: one stage per pass).  x stays in registers in natural dim order (the uniform
 // dim index d_p addresses it through M0-relative moves).
 #pragma once
+#include "coupling_r16.h"
 
 namespace naz {
 
@@ -43,12 +42,7 @@ constexpr int ar_round_half_even(double v) {
 }
 
 constexpr int kARCap = 20480;  // floats per ring slot at most (2 slots = 160 KB, one workgroup per CU)
-#ifndef NAZ_AR_INV_NW
-#define NAZ_AR_INV_NW 12
-#endif
-#ifndef NAZ_AR_INV_CAP
-#define NAZ_AR_INV_CAP kARCap  // the inverse's per-stage cap (CfgAR::make_layout)
-#endif
+constexpr int kARInvWaves = 12;  // the inverse's workgroup where three waves per SIMD fit (CfgAR::NW)
 
 // The inverse select-first spline of ONE dim per row, spread over the row's four lanes (quarters q
 // = lane >> 4 of the 16-row MFMA layout) instead of evaluated four times.  The output blocks of
@@ -189,7 +183,7 @@ struct CfgAR {
       int run = 0;
       for (int i = 0; i <= NHID; ++i) {
         const int sz = sub_floats_of(y, p, i);
-        if (i == 0 || run + sz > NAZ_AR_INV_CAP) {
+        if (i == 0 || run + sz > kARCap) {
           ++s;
           run = 0;
         }
@@ -241,28 +235,16 @@ struct CfgAR {
   // forward kernel's workgroup (CfgARF) keeps one workgroup per CU of 4 x WPE waves
   static constexpr int WPE = NHID * KSH <= 8 ? 3 : 2;
   static constexpr int NW_FWD = 4 * WPE;
-  // inverse workgroup: NAZ_AR_INV_NW waves (12: one workgroup per CU; 6 with NAZ_AR_INV_CAP =
-  // 10240: two per CU, each on its own 2 x <= 40 KB ring, so the two do not share barriers)
-  static constexpr int NW = WPE == 3 ? NAZ_AR_INV_NW : NW_FWD;
-  // the inverse kernel's waves per SIMD (NAZ_AR_INV_WPE overrides: e.g. 2 with NAZ_AR_INV_NW = 8)
-  // and its prefetched MFMA chains (NAZ_AR_INV_PF: mfma3_16_chain_lds)
-#ifdef NAZ_AR_INV_WPE
-  static constexpr int WPE_INV = WPE == 3 ? NAZ_AR_INV_WPE : WPE;
-#else
-  static constexpr int WPE_INV = WPE;
-#endif
-#ifdef NAZ_AR_INV_PF
-  static constexpr bool PF = true;
-#else
-  static constexpr bool PF = false;
-#endif
+  // inverse workgroup: one per CU (the A/B'd alternatives — 6 waves on 2 x 40 KB rings, two per
+  // CU; 8 waves at 2 per SIMD; prefetched MFMA chains, mfma3_16_chain_lds — were not kept)
+  static constexpr int NW = WPE == 3 ? kARInvWaves : NW_FWD;
   static_assert(H <= 256 && D <= 32 && D >= 2 && NHID >= 1 && NHID <= 3, "unsupported fused autoregressive shape");
   static_assert(NOB <= 2 && NSTG <= 128, "output blocks / stages");
 };
 
 // acc += sum over t < N of (A fragment t at LDS byte address ub + 2048 t, hi | lo 1 KB apart) x
 // bset[t] on the f16x3 16-row MFMA.  Fragment t + 1 is read while fragment t's MFMAs run (untracked
-// reads with a counted wait, coupling.hip's lds_read_b128_untracked): for the one-wave-per-SIMD
+// reads with a counted wait, lds_ring.h's lds_read_b128_untracked): for the one-wave-per-SIMD
 // wide MADE kernels, which have no other wave to hide an LDS read behind.
 template <int N, class BS>
 NAZ_DEV floatx4 mfma3_16_chain_lds(unsigned ub, const BS& bset, floatx4 acc) {
@@ -390,12 +372,12 @@ NAZ_DEV void ar_split4(Frag2& f, const floatx4& a) {
 }
 
 template <class CF>
-__global__ void __launch_bounds__(64 * CF::NW, CF::WPE_INV) made_ar_r16_kernel(
+__global__ void __launch_bounds__(64 * CF::NW, CF::WPE) made_ar_r16_kernel(
     const float* __restrict__ packed, int L, const float* __restrict__ x, int64_t ldx,
     const float* __restrict__ ctx, int64_t ldc, const float* __restrict__ low, const float* __restrict__ high,
     float* __restrict__ out_lp, int64_t B, float bound, int64_t spk = 0, int64_t sx = 0, int64_t slp = 0,
     int c0mode = 0, float* __restrict__ states = nullptr) {
-  constexpr int D = CF::D, K = CF::K, P = CF::P, NW = CF::NW, NHID = CF::NHID;
+  constexpr int D = CF::D, K = CF::K, NW = CF::NW, NHID = CF::NHID;
   {  // blockIdx.y = draw (naz_ar_flow_log_prob_batched): image packed + draw spk, rows x + draw sx
     const int64_t dz = blockIdx.y;
     packed += dz * spk;
@@ -495,7 +477,6 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::WPE_INV) made_ar_r16_kernel(
           const int base = (OFF >> 2) + idx * 128 + lane;
           return Frag2{__builtin_bit_cast(half8, c4[base]), __builtin_bit_cast(half8, c4[base + 64])};
         };
-        [[maybe_unused]] const unsigned ub = (unsigned)(uintptr_t)to_lds(cur) + 16u * lane + 4u * OFF;
         const float4* bias4 = reinterpret_cast<const float4*>(cur + OFF_BIAS);
         bool done0 = false;
         if constexpr (p == 0) {
@@ -564,12 +545,8 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::WPE_INV) made_ar_r16_kernel(
             constexpr int bi = decltype(bc)::value, b = BLO + bi;
             const float4 bv = bias4[4 * bi + q];
             floatx4 acc = floatx4{bv.x, bv.y, bv.z, bv.w};
-            if constexpr (CF::PF) {
-              acc = mfma3_16_chain_lds<KT>(ub + 2048u * (bi * KT), hf[i - 1], acc);
-            } else {
 #pragma unroll
-              for (int t = 0; t < KT; ++t) acc = mfma3_16(afrag(bi * KT + t), hf[i - 1][t], acc);
-            }
+            for (int t = 0; t < KT; ++t) acc = mfma3_16(afrag(bi * KT + t), hf[i - 1][t], acc);
             ar_split4<b & 1>(hf[i][b >> 1], acc);
           });
         } else if constexpr (i == NHID) {
@@ -580,15 +557,10 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::WPE_INV) made_ar_r16_kernel(
               const float4 bv = bias4[4 * o + q];
               o3[o] = floatx4{bv.x, bv.y, bv.z, bv.w};
             }
-            if constexpr (CF::PF) {
 #pragma unroll
-              for (int o = 0; o < CF::NOB; ++o) o3[o] = mfma3_16_chain_lds<KT>(ub + 2048u * (o * KT), hf[NHID - 1], o3[o]);
-            } else {
+            for (int t = 0; t < KT; ++t)
 #pragma unroll
-              for (int t = 0; t < KT; ++t)
-#pragma unroll
-                for (int o = 0; o < CF::NOB; ++o) o3[o] = mfma3_16(afrag(o * KT + t), hf[NHID - 1][t], o3[o]);
-            }
+              for (int o = 0; o < CF::NOB; ++o) o3[o] = mfma3_16(afrag(o * KT + t), hf[NHID - 1][t], o3[o]);
           }
           const float y = v[dp];
           if constexpr (CF::AFFINE) {
@@ -600,26 +572,11 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::WPE_INV) made_ar_r16_kernel(
             xmax = fmaxf(xmax, fabsf(v[dp]));
             ldsum += ls;
           } else {
-#ifndef NAZ_AR_SPLINE_GATHER
-            // one spline per row spread over its four quarters (rqs_select_inv_quad)
+            // one spline per row spread over its four quarters (rqs_select_inv_quad), not gathered
+            // into and evaluated by every quarter
             float ld;
             v[dp] = rqs_select_inv_quad<K>(o3[0], o3[CF::NOB > 1 ? 1 : 0], q, y, bound, rc, ld);
             ldsum -= ld;
-#else
-            // (A/B) every quarter gathers the row's parameters and evaluates the whole spline:
-            // parameter pi sits in block pi >> 4, register pi & 3 of quarter (pi & 15) >> 2
-            float uw[K], uh[K], ud[K - 1];
-#pragma unroll
-            for (int pi = 0; pi < P; ++pi) {
-              const float val = __shfl(o3[pi >> 4][pi & 3], (lane & 15) + 16 * ((pi & 15) >> 2));
-              if (pi < K) uw[pi] = val;
-              else if (pi < 2 * K) uh[pi - K] = val;
-              else ud[pi - 2 * K] = val;
-            }
-            float ld;
-            v[dp] = rqs_select<K, true>(uw, uh, ud, y, bound, rc, ld);
-            ldsum -= ld;
-#endif
           }
         }
       });
@@ -715,11 +672,7 @@ struct CfgARF {
     return y;
   }
   static constexpr KtTab KTT = make_kt();
-#ifdef NAZ_AR_FWD_DENSE_K  // (A/B: every hidden block reads all KSH k-steps)
-  static constexpr int hid_kts(int) { return KSH; }
-#else
   static constexpr int hid_kts(int b) { return KTT.kt[b]; }
-#endif
   static constexpr int unit_kts(int u) { return u < HB ? KI : (u < NHID * HB ? hid_kts(u % HB) : KSH); }
   static constexpr int unit_floats(int u) { return unit_blocks(u) * (unit_kts(u) * OT + 16); }
   struct Layout {

@@ -2,8 +2,7 @@
 // examples/papers/2506.05657/train_mle_all_data_4param.py:87-92; POSYDON D=4, 512x5, L=16,
 // eposydon/train_maf_mle.py:84-90): pyro ConditionedAffineAutoregressive._inverse (naz
 // flows/transforms.py:133-160) over every layer, driven by NormalizingFlow.log_prob (flow.py:45-79),
-// in ONE launch.  Included by coupling.hip after made_ar_r16.h (CfgARW, Frag2, ar_split4, mfma3_16,
-// r16_feat, stage_issue, ring_barrier, ar_piece / ar_piece_dev).
+// in ONE launch, over made_ar_r16.h's CfgARW, ar_split4 and ar_piece / ar_piece_dev.
 //
 // made_ar_r16_kernel computes every MADE hidden unit once, in the pass of its mask degree, and keeps
 // all hidden layers as register-resident B fragments.  At H = 512 one hidden layer is 16 fragments =
@@ -26,10 +25,7 @@
 // output unit: the (mean, log_scale) rows of dim perm[p]; then x[perm[p]] = (y - mean) exp(-clamp(ls))
 // on every quarter (pyro AffineAutoregressive._inverse), as made_ar_r16_kernel's affine epilogue.
 #pragma once
-
-#ifndef NAZ_HD
-#define NAZ_HD __host__ __device__ inline
-#endif
+#include "made_ar_r16.h"
 
 namespace naz {
 
@@ -127,7 +123,7 @@ struct CfgARIW {
 // value of word-slot (m, kg, j) of fragment t of unit u (dim dp for the output rows); wv(i, idx) =
 // the masked weight idx of sub-layer i in the flat layout (made_ar_pack_layer's)
 template <class CF, class WV>
-NAZ_HD float ariw_weight(int u, int t, int m, int kg, int j, int dp, const WV& wv) {
+__host__ __device__ inline float ariw_weight(int u, int t, int m, int kg, int j, int dp, const WV& wv) {
   constexpr int D = CF::D, C = CF::C, H = CF::H, P = CF::P;
   const int i = CF::LY.ui[u], b = CF::LY.ub[u];
   if (i == CF::NHID) {
@@ -150,7 +146,7 @@ NAZ_HD float ariw_weight(int u, int t, int m, int kg, int j, int dp, const WV& w
 
 // bias slot r (0..15) of unit u: bv(i, idx) = bias idx of sub-layer i
 template <class CF, class BV>
-NAZ_HD float ariw_bias(int u, int r, int dp, const BV& bv) {
+__host__ __device__ inline float ariw_bias(int u, int r, int dp, const BV& bv) {
   const int i = CF::LY.ui[u], b = CF::LY.ub[u];
   if (i == CF::NHID) return r < CF::P ? bv(i, r * CF::D + dp) : 0.f;
   const int un = 16 * b + r;

@@ -36,9 +36,7 @@ constexpr float kMinLambda = 0.025f;  // rational-linear spline (rls.hip): Î» âˆ
 // scoreboard (after an opaque asm wait it re-waits vmcnt(0) at the first use of a register loaded
 // before the barrier â€” which then also waits for the DMAs issued after it).
 NAZ_DEV void ring_barrier() {
-#ifndef NAZ_ABL_RING_NOWAIT  // A/B only: the round-2 (racy) form
   __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
   __syncthreads();
 }
 

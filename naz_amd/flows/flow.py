@@ -40,7 +40,7 @@ class _FusedCoupling:
     (tracked by tensor version counters), so inference pays it once."""
 
     # fp16 pieces of the PACKED GEMM2/3 weights must stay finite with margin: |W'| < 2^15.  The
-    # packer's sigmoid fold scales W1 by -2*(2 log2 e) and W2 by -2 (coupling.hip, kSigScale).
+    # packer's sigmoid fold scales W1 by -2*(2 log2 e) and W2 by -2 (coupling_x6.h, kSigScale).
     F16_WEIGHT_LIMIT = 32768.0
     F16_PACK_SCALE = {1: 2.0 * 2.88539008177792681, 2: 2.0}
 
