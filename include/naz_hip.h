@@ -539,6 +539,37 @@ int naz_ar_flow_bwd_layer(const naz_ar_desc* d, const void* packed_fwd, const vo
                           int layer, const float* state, const float* ctx, int64_t ldc, const float* g_in,
                           const float* g_lp, float* const* bufs, float* g_out, int64_t B, void* stream);
 
+/* ---- fused nsa backward: the NLL step of a spline autoregressive flow ------------------------
+ * Replaces loss.backward() of an nsa NLL (naz/trainers/train_flows.py:194-213 over
+ * neural_spline_autoregressive, transforms.py:165-198) at the compiled shape (naz's own nsa flow,
+ * D=4 | C=2, H=[128,128], K=8; naz_spline_ar_flow_bwd_packed_bytes < 0 otherwise).  The family
+ * mirrors the affine one above and shares its image layouts; kind must be NAZ_AR_SPLINE.
+ *   naz_spline_ar_flow_log_prob_train: naz_ar_flow_log_prob (one draw, no bounding) of any spline
+ *     flow whose inverse is fused, also writing states [L][B][D]: states[l] = s_l, layer l's output.
+ *   naz_spline_ar_flow_pack_bwd: per-layer backward images from the naz_ar_flow_pack_host flat
+ *     layout on the device; mask (nullable, same layout) multiplies.
+ *   naz_spline_ar_flow_bwd_dims: dims[7] = {n_hidden, HP, XA, XB, X0W, GOW, rows per tile}.
+ *   naz_spline_ar_flow_bwd_layer: layer `layer`'s backward (call l = 0 .. L-1): g_in [B][D] =
+ *     dL/ds_l, g_lp [B] = dL/dlog p (nullable: 1), state_out = s_l = states[layer], state_in =
+ *     s_{l+1} (states[layer + 1]; the flow's input x, contiguous [B][D], for the last layer),
+ *     packed_fwd = the naz_ar_flow_pack_fwd image, perm = [L][D] dim of order p; writes g_out
+ *     [B][D] = dL/ds_{l+1} and the operands bufs[2 + 3 n_hidden] in the affine family's order: x0
+ *     [B][X0W], per hidden layer i (h_i [B][XA], [B][XB]: null when XB = 0), per hidden layer i
+ *     dp_i [B][HP], then gout [B][GOW] = dL/d ARN output row (pi D + d) in columns pi D + d, zero
+ *     padded.  dW_0 = dp_1ᵀ x0, dW_i = dp_{i+1}ᵀ h_i, dW_out = goutᵀ h_n, biases = column sums.
+ *     A dim with |s_{l+1}[d]| > bound is the identity: exact zeros in every operand, g passed on. */
+int naz_spline_ar_flow_log_prob_train(const naz_ar_desc* d, const void* packed, const float* x, int64_t ldx,
+                                      const float* ctx, int64_t ldc, float* out_lp, float* states, int64_t B,
+                                      void* stream);
+int64_t naz_spline_ar_flow_bwd_packed_bytes(const naz_ar_desc* d);
+int naz_spline_ar_flow_bwd_dims(const naz_ar_desc* d, int* dims);
+int naz_spline_ar_flow_pack_bwd(const naz_ar_desc* d, const float* flat, const float* mask, void* packed,
+                                void* stream);
+int naz_spline_ar_flow_bwd_layer(const naz_ar_desc* d, const void* packed_fwd, const void* packed_bwd, const int* perm,
+                                 int layer, const float* state_out, const float* state_in, const float* ctx,
+                                 int64_t ldc, const float* g_in, const float* g_lp, float* const* bufs, float* g_out,
+                                 int64_t B, void* stream);
+
 /* ---- §8b: whole-flow entries over the fused kinds -------------------------------------
  * One descriptor for the flows whose whole log_prob is one launch: the spline coupling flow (naz
  * "nsc": naz_coupling_*) and the autoregressive flows (naz "nsa" / "maf": naz_ar_flow_*).  The

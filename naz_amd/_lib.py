@@ -132,6 +132,12 @@ SIGNATURES = {
     "naz_ar_flow_pack_bwd": (C.c_int, [C.POINTER(ArDesc), _vp, _vp, _vp, _vp]),
     "naz_ar_flow_bwd_layer": (C.c_int, [C.POINTER(ArDesc), _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                         _i64, _vp]),
+    "naz_spline_ar_flow_log_prob_train": (C.c_int, [C.POINTER(ArDesc), _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "naz_spline_ar_flow_bwd_packed_bytes": (C.c_int64, [C.POINTER(ArDesc)]),
+    "naz_spline_ar_flow_bwd_dims": (C.c_int, [C.POINTER(ArDesc), _vp]),
+    "naz_spline_ar_flow_pack_bwd": (C.c_int, [C.POINTER(ArDesc), _vp, _vp, _vp, _vp]),
+    "naz_spline_ar_flow_bwd_layer": (C.c_int, [C.POINTER(ArDesc), _vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp,
+                                               _vp, _vp, _i64, _vp]),
     "naz_ar_flow_sample": (C.c_int, [C.POINTER(ArDesc), _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64,
                                      _vp]),
     "naz_flow_packed_bytes": (C.c_int64, [C.POINTER(FlowDesc)]),

@@ -104,6 +104,12 @@ static ImgSpec spec_ar(const naz_ar_desc* d, uint32_t kind) {
                             (uint32_t)d->kind}),
           d->L, b};
 }
+// the spline family's backward image: the autoregressive-backward kind under the spline descriptor's tag
+static ImgSpec spec_ar_spline_bwd(const naz_ar_desc* d) {
+  ImgSpec sp = spec_ar(d, IMG_AR_BWD);
+  if (d != nullptr) sp.body = spline_ar_flow_bwd_packed_bytes(d);
+  return sp;
+}
 static ImgSpec spec_cnf(const naz_cnf_desc* d) {
   if (d == nullptr) return {IMG_CNF, 0, 0, -1};
   uint32_t hs[4] = {};
@@ -728,6 +734,59 @@ int naz_ar_flow_bwd_layer(const naz_ar_desc* d, const void* packed_fwd, const vo
   NAZ_IMG("naz_ar_flow_bwd_layer", spec_ar(d, IMG_AR_BWD), packed_bwd, 1, 0, 0, body_bwd);
   return ar_flow_bwd_layer(d, body_fwd, body_bwd, perm, layer, state, ctx, ldc, g_in, g_lp, bufs, g_out, B,
                            as_stream(stream));
+}
+
+// ---- fused nsa backward (made_ar_bwd.h, spline instance): the nsa NLL step ----------------
+int naz_spline_ar_flow_log_prob_train(const naz_ar_desc* d, const void* packed, const float* x, int64_t ldx,
+                                      const float* ctx, int64_t ldc, float* out_lp, float* states, int64_t B,
+                                      void* stream) {
+  if (B < 0) return set_error("naz_spline_ar_flow_log_prob_train: negative batch");
+  if (B > 0 && (packed == nullptr || x == nullptr || out_lp == nullptr || states == nullptr))
+    return set_error("naz_spline_ar_flow_log_prob_train: null pointer");
+  if (d != nullptr && d->C > 0 && B > 0 && ctx == nullptr)
+    return set_error("naz_spline_ar_flow_log_prob_train: conditional flow needs ctx");
+  if (d == nullptr || d->kind != NAZ_AR_SPLINE || naz_ar_flow_supported(d) != 1)
+    return set_error("naz_spline_ar_flow_log_prob_train: no fused spline inverse for this flow");
+  if (B == 0) return 0;
+  NAZ_IMG("naz_spline_ar_flow_log_prob_train", spec_ar(d, IMG_AR_INV), packed, 1, 0, 0, body);
+  return spline_ar_flow_log_prob_train(d, body, x, ldx, ctx, ldc, out_lp, states, B, as_stream(stream));
+}
+int64_t naz_spline_ar_flow_bwd_packed_bytes(const naz_ar_desc* d) {
+  return img_bytes(spline_ar_flow_bwd_packed_bytes(d));
+}
+int naz_spline_ar_flow_bwd_dims(const naz_ar_desc* d, int* dims) { return spline_ar_flow_bwd_dims(d, dims); }
+int naz_spline_ar_flow_pack_bwd(const naz_ar_desc* d, const float* flat, const float* mask, void* packed,
+                                void* stream) {
+  const ImgSpec sp = spec_ar_spline_bwd(d);
+  if (sp.body < 0) {  // no backward instance: report the descriptor
+    int dims[7];
+    return spline_ar_flow_bwd_dims(d, dims);
+  }
+  if (flat == nullptr || packed == nullptr) return set_error("naz_spline_ar_flow_pack_bwd: null pointer");
+  if (int rc = spline_ar_flow_pack_bwd(d, flat, mask, static_cast<char*>(packed) + kImgHdr, as_stream(stream)))
+    return rc;
+  return img_publish("naz_spline_ar_flow_pack_bwd", sp, packed, img_bytes(sp.body), 1, 0, as_stream(stream));
+}
+int naz_spline_ar_flow_bwd_layer(const naz_ar_desc* d, const void* packed_fwd, const void* packed_bwd, const int* perm,
+                                 int layer, const float* state_out, const float* state_in, const float* ctx,
+                                 int64_t ldc, const float* g_in, const float* g_lp, float* const* bufs, float* g_out,
+                                 int64_t B, void* stream) {
+  if (B < 0) return set_error("naz_spline_ar_flow_bwd_layer: negative batch");
+  if (B > 0 && (packed_fwd == nullptr || packed_bwd == nullptr || perm == nullptr || state_out == nullptr ||
+                state_in == nullptr || g_in == nullptr || bufs == nullptr || g_out == nullptr))
+    return set_error("naz_spline_ar_flow_bwd_layer: null pointer");
+  if (d != nullptr && d->C > 0 && B > 0 && ctx == nullptr)
+    return set_error("naz_spline_ar_flow_bwd_layer: conditional flow needs ctx");
+  if (d == nullptr || layer < 0 || layer >= d->L) return set_error("naz_spline_ar_flow_bwd_layer: layer out of range");
+  if (spline_ar_flow_bwd_packed_bytes(d) < 0) {  // no backward instance (or not a spline flow): report the descriptor
+    int dims[7];
+    return spline_ar_flow_bwd_dims(d, dims);
+  }
+  if (B == 0) return 0;
+  NAZ_IMG("naz_spline_ar_flow_bwd_layer", spec_ar(d, IMG_AR_FWD), packed_fwd, 1, 0, 0, body_fwd);
+  NAZ_IMG("naz_spline_ar_flow_bwd_layer", spec_ar_spline_bwd(d), packed_bwd, 1, 0, 0, body_bwd);
+  return spline_ar_flow_bwd_layer(d, body_fwd, body_bwd, perm, layer, state_out, state_in, ctx, ldc, g_in, g_lp, bufs,
+                                  g_out, B, as_stream(stream));
 }
 
 // ---- §8b whole-flow entries over the fused kinds ----------------------------------------

@@ -341,4 +341,17 @@ int ar_flow_log_prob_train(const naz_ar_desc* d, const void* packed, const float
   return rc == -2 ? ar_unsupported(d) : rc;
 }
 
+// the nsa training forward: the spline instances of made_ar_r16_kernel with their per-layer outputs saved
+int spline_ar_flow_log_prob_train(const naz_ar_desc* d, const void* packed, const float* x, int64_t ldx,
+                                  const float* ctx, int64_t ldc, float* out_lp, float* states, int64_t B,
+                                  hipStream_t s) {
+  if (states == nullptr) return set_error("naz_spline_ar_flow_log_prob_train: null states");
+  if (d == nullptr || d->kind != NAZ_AR_SPLINE) return ar_unsupported(d);
+  const int rc = ar_dispatch(d, [&](auto ops) {
+    return decltype(ops)::log_prob(static_cast<const float*>(packed), d->L, x, ldx, ctx, ldc, nullptr, nullptr, out_lp,
+                                   B, d->bound, s, 1, 0, 0, 0, 0, states, nullptr, 0);
+  });
+  return rc == -2 ? ar_unsupported(d) : rc;
+}
+
 }  // namespace naz

@@ -215,24 +215,33 @@ class _FusedAR:
         return ops.absmax(x, context) < self.F16_DATA_LIMIT
 
     def train_ready(self, x, context) -> bool:
-        """The maf NLL step on the fused backward (made_ar_bwd.h, flows/maf_grad.py): an affine flow
-        at a compiled shape, rows inside the f16 split's range, no gradient wanted for x or the
-        context (train's data).  NAZ_TRAIN_FUSED=0 keeps the autograd walk."""
-        if self.kind != "maf" or _TRAIN_FUSED == "0" or x.dim() != 2 or x.requires_grad or \
+        """The NLL step on a fused backward: an affine ("maf") flow on made_ar_bwd.h's affine instances
+        (flows/maf_grad.py) or the GEMM-composed wide backward, or a spline ("nsa") flow at the
+        compiled shape of made_ar_bwd.h's spline instance (naz's own D=4 | C=2, H=[128,128], K=8;
+        flows/nsa_grad.py: a saved-state forward plus one backward launch per layer).  Conditions:
+        rows and context inside the f16 split's range, no gradient wanted for x or the context
+        (train's data).  Everything else keeps the autograd walk: other nsa shapes, order="linear",
+        active dropout, Permute layers and per-dim log-dets (their callers never reach the fused
+        plan).  NAZ_TRAIN_FUSED=0 keeps the walk everywhere."""
+        if self.kind not in ("maf", "nsa") or _TRAIN_FUSED == "0" or x.dim() != 2 or x.requires_grad or \
                 (context is not None and context.requires_grad) or not self._train_kernels():
             return False
         return self.log_prob_ready(x, context)
 
     def _train_kernels(self) -> bool:
-        """The fused backward kernel (made_ar_bwd.h) at its compiled shapes; elsewhere a fused inverse
-        (naz_ar_flow_log_prob_train) + the GEMM-composed backward (flows/maf_grad_wide.py).
-        NAZ_TRAIN_WIDE=0 keeps the autograd walk at the latter's shapes."""
+        """maf: the fused backward kernel (made_ar_bwd.h) at its compiled shapes; elsewhere a fused
+        inverse (naz_ar_flow_log_prob_train) + the GEMM-composed backward (flows/maf_grad_wide.py;
+        NAZ_TRAIN_WIDE=0 keeps the autograd walk at the latter's shapes).  nsa: the spline instance
+        of the fused backward kernel, where compiled (naz_spline_ar_flow_bwd_packed_bytes > 0)."""
+        if self.kind == "nsa":
+            return self.inverse and ops.spline_ar_flow_bwd_supported(self.desc)
         if ops.ar_flow_bwd_supported(self.desc):
             return True
         return _TRAIN_WIDE != "0" and self.inverse and ops.ar_flow_supported(self.desc) == 1
 
     def maf_grad(self):
-        """MafGrad for the current permutations and masks (rebuilt when one of them changes)."""
+        """MafGrad / WideMafGrad / NsaGrad for the current permutations and masks (rebuilt when one of
+        them changes)."""
         nets = self._nets()
         ts = [t for n in nets for l in n.layers for t in (l.mask,)] + [n.permutation for n in nets]
         cz = any(bool(getattr(n, "clip_zero_grad", False)) for n in nets)  # jnp.clip's gradient (bflow)
@@ -243,7 +252,11 @@ class _FusedAR:
             mask = torch.cat([t for n in nets for l in n.layers
                               for t in (l.mask.detach().reshape(-1).float(), torch.ones_like(l.bias.detach()))])
             perm = np.stack([n.permutation.detach().cpu().numpy() for n in nets]).astype(np.int32)
-            cls = MafGrad if ops.ar_flow_bwd_supported(self.desc) else WideMafGrad
+            if self.kind == "nsa":
+                from .nsa_grad import NsaGrad
+                cls = NsaGrad
+            else:
+                cls = MafGrad if ops.ar_flow_bwd_supported(self.desc) else WideMafGrad
             self._mg = (sig, cls(self.desc, perm, mask.contiguous(), clip_zero=cz))
         return self._mg[1]
 
@@ -251,7 +264,7 @@ class _FusedAR:
         return [p for n in self._nets() for l in n.layers for p in (l.weight, l.bias)]
 
     def train_log_prob(self, x, context=None, bounds=None):
-        """log p(x | ctx) recorded as ONE autograd node whose backward is the fused maf backward."""
+        """log p(x | ctx) recorded as ONE autograd node whose backward is the fused maf / nsa backward."""
         lj = None
         if bounds is not None:  # naz bounding_transform: a constant of the parameters here
             with torch.no_grad():
@@ -372,9 +385,10 @@ _AR_PASS0 = __import__("os").environ.get("NAZ_AR_PASS0", "1") != "0"  # one-cont
 
 
 class _MafTrainFn(torch.autograd.Function):
-    """NormalizingFlow.log_prob of a maf flow under autograd at the fused backward's shapes (naz
-    train's loss, train_flows.py:195, 208): forward = the fused inverse kernel with every layer's
-    output saved; backward = one fused backward launch per layer + batched dW (flows/maf_grad.py)."""
+    """NormalizingFlow.log_prob of a maf or nsa flow under autograd at the fused backward's shapes
+    (naz train's loss, train_flows.py:195, 208): forward = the fused inverse kernel with every
+    layer's output saved; backward = one fused backward launch per layer + batched dW
+    (flows/maf_grad.py, flows/nsa_grad.py: generic over the grad object)."""
 
     @staticmethod
     def forward(ctx, x, context, plan, *params):

@@ -1066,6 +1066,91 @@ def ar_flow_bwd_layer(d: ArDesc, packed_fwd: Tensor, packed_bwd: Tensor, perm: T
           "ar_flow_bwd_layer")
 
 
+# ----------------------------------------------------------------------------- fused nsa backward
+def spline_ar_flow_bwd_supported(d: ArDesc) -> bool:
+    """The fused nsa backward (made_ar_bwd.h, spline instance) is compiled for this shape."""
+    return int(lib().naz_spline_ar_flow_bwd_packed_bytes(d)) > 0
+
+
+def spline_ar_flow_bwd_dims(d: ArDesc) -> dict:
+    """Operand widths of naz_spline_ar_flow_bwd_layer (include/naz_hip.h)."""
+    out = np.zeros(7, dtype=np.int32)
+    check(lib().naz_spline_ar_flow_bwd_dims(d, out.ctypes.data), "spline_ar_flow_bwd_dims")
+    return dict(zip(("n_hidden", "HP", "XA", "XB", "X0W", "GOW", "rows"), (int(v) for v in out)))
+
+
+def spline_ar_flow_pack_bwd(d: ArDesc, flat: Tensor, mask: Optional[Tensor] = None) -> Tensor:
+    """Per-layer backward images (naz_spline_ar_flow_pack_bwd) of one nsa flow's flat [L * per] parameters."""
+    dev = _dev(flat, mask)
+    flat = flat.reshape(-1).contiguous()
+    n = int(lib().naz_spline_ar_flow_bwd_packed_bytes(d)) // 4
+    if n <= 0:
+        raise RuntimeError("naz_amd spline_ar_flow_pack_bwd: unsupported descriptor")
+    if mask is not None and (mask.numel() != flat.numel() or not mask.is_contiguous()):
+        raise ValueError("spline_ar_flow_pack_bwd: mask must be a contiguous tensor shaped like flat")
+    out = torch.empty(n, device=dev, dtype=torch.float32)
+    check(lib().naz_spline_ar_flow_pack_bwd(d, _p(flat), _p(mask), _p(out), _stream(dev)), "spline_ar_flow_pack_bwd")
+    return track_image(out)
+
+
+def spline_ar_flow_log_prob_train(d: ArDesc, packed: Tensor, x: Tensor, context: Optional[Tensor], states: Tensor,
+                                  out: Optional[Tensor] = None) -> Tensor:
+    """log p(x | ctx) of an nsa flow (the inverse image) also writing states [L, B, D]: layer l's
+    output s_l, for naz_spline_ar_flow_bwd_layer."""
+    dev = _dev(packed, x, context, states, out)
+    x, ldx = _rows(x)
+    B = x.shape[0]
+    context, ldc = _ctx_arg(context, B)
+    if states.shape != (d.L, B, d.D) or not states.is_contiguous() or states.dtype != torch.float32:
+        raise ValueError(f"spline_ar_flow_log_prob_train: states must be contiguous float32 {(d.L, B, d.D)}")
+    if out is None:
+        out = torch.empty((B,), device=dev, dtype=torch.float32)
+    check(lib().naz_spline_ar_flow_log_prob_train(d, _p(packed), _p(x), ldx, _p(context), ldc, _p(out), _p(states), B,
+                                                  _stream(dev)), "spline_ar_flow_log_prob_train")
+    return out
+
+
+def spline_ar_flow_bwd_layer(d: ArDesc, packed_fwd: Tensor, packed_bwd: Tensor, perm: Tensor, layer: int,
+                             state_out: Tensor, state_in: Tensor, context: Optional[Tensor], g_in: Tensor,
+                             g_lp: Optional[Tensor], bufs: List[Tensor], g_out: Tensor) -> None:
+    """Layer ``layer``'s fused nsa backward (naz_spline_ar_flow_bwd_layer): state_out = s_l, state_in =
+    s_{l+1} (the flow's input for the last layer); g_in = dL/ds_l -> g_out = dL/ds_{l+1} and the
+    weight-gradient operands ``bufs`` (include/naz_hip.h order)."""
+    dev = _dev(packed_fwd, packed_bwd, state_out, state_in, context, g_in, g_lp, g_out)
+    if perm.dtype != torch.int32 or perm.device != dev or perm.shape != (d.L, d.D):
+        raise ValueError(f"spline_ar_flow_bwd_layer: perm must be an int32 [{d.L}, {d.D}] tensor on {dev}")
+    B = state_out.shape[0]
+    context, ldc = _ctx_arg(context, B)
+    for t in (state_out, state_in, g_in, g_out, perm) + tuple(b for b in bufs if b is not None) + \
+            ((g_lp,) if g_lp is not None else ()):
+        if not t.is_contiguous():
+            raise ValueError("spline_ar_flow_bwd_layer: buffers must be contiguous")
+    if not (0 <= int(layer) < d.L):
+        raise ValueError(f"spline_ar_flow_bwd_layer: layer {layer} outside [0, {d.L})")
+    for name, t in (("state_out", state_out), ("state_in", state_in), ("g_in", g_in), ("g_out", g_out)):
+        if t.dim() != 2 or t.shape[0] != B or t.shape[1] != d.D or t.dtype != torch.float32:
+            raise ValueError(f"spline_ar_flow_bwd_layer: {name} must be float32 [{B}, {d.D}], got {tuple(t.shape)}")
+    if g_lp is not None and (g_lp.numel() != B or g_lp.dtype != torch.float32):
+        raise ValueError(f"spline_ar_flow_bwd_layer: g_lp must be float32 [{B}]")
+    dm = spline_ar_flow_bwd_dims(d)
+    NH, HP, X0W, XA, XB, GOW = dm["n_hidden"], dm["HP"], dm["X0W"], dm["XA"], dm["XB"], dm["GOW"]
+    if len(bufs) != 2 + 3 * NH:
+        raise ValueError(f"spline_ar_flow_bwd_layer: {2 + 3 * NH} operand buffers expected, got {len(bufs)}")
+    widths = [X0W] + [w for _ in range(NH) for w in (XA, XB)] + [HP] * NH + [GOW]
+    for k, (t, w) in enumerate(zip(bufs, widths)):
+        if t is None:
+            if w != 0 and not (1 <= k <= 2 * NH and k % 2 == 0 and XB == 0):
+                raise ValueError(f"spline_ar_flow_bwd_layer: operand buffer {k} is required")
+            continue
+        if t.dim() != 2 or t.shape[0] < B or t.shape[1] != w or t.dtype != torch.float32 or t.device != dev:
+            raise ValueError(f"spline_ar_flow_bwd_layer: operand buffer {k} must be float32 [>= {B}, {w}] on {dev}, "
+                             f"got {tuple(t.shape)}")
+    ptrs = (C.c_void_p * len(bufs))(*[_p(b) for b in bufs])
+    check(lib().naz_spline_ar_flow_bwd_layer(d, _p(packed_fwd), _p(packed_bwd), _p(perm), int(layer), _p(state_out),
+                                             _p(state_in), _p(context), ldc, _p(g_in), _p(g_lp), ptrs, _p(g_out), B,
+                                             _stream(dev)), "spline_ar_flow_bwd_layer")
+
+
 # ----------------------------------------------------------------------------- a10: fused NLL step
 # ----------------------------------------------------------------------------- §8b whole-flow entries
 def flow_desc(part) -> FlowDesc:

@@ -5,7 +5,12 @@
 Compares the gfx950 kernel symbols, every kernel's instruction sequence (addresses relative to the
 kernel's start), every kernel's code-object metadata (vgpr, agpr, sgpr, spills, scratch, LDS) and
 the exported names (nm -D --defined-only, hipcc's per-unit __hip_cuid_ ids aside).  Exit status
-0 = identical.
+0 = identical.  For an additive change (new kernels, new entry points, nothing existing touched):
+
+    python scripts/compare_libs.py --allow-new <old.so> <new.so>
+
+lists the kernels and exports that exist only in the new library without counting them; anything
+missing from the new library, or different in both, still fails.
 """
 import re
 import subprocess
@@ -59,12 +64,17 @@ def exports(lib: Path) -> list:
 
 
 def main() -> int:
-    old, new = Path(sys.argv[1]), Path(sys.argv[2])
+    args = [a for a in sys.argv[1:] if a != "--allow-new"]
+    allow_new = len(args) != len(sys.argv) - 1
+    old, new = Path(args[0]), Path(args[1])
     ko, kn = kernels(old), kernels(new)
-    bad = 0
+    bad = added = 0
     for name in sorted(set(ko) ^ set(kn)):
         print(f"kernel only in {'old' if name in ko else 'new'}: {name}")
-        bad += 1
+        if allow_new and name in kn:
+            added += 1
+        else:
+            bad += 1
     ninsn = 0
     for name in sorted(set(ko) & set(kn)):
         (so, mo), (sn, mn) = ko[name], kn[name]
@@ -81,9 +91,13 @@ def main() -> int:
     for name in sorted(set(eo) ^ set(en)):
         kind = "C++ export" if name.startswith("_Z") else "C export"  # the API is the C names (naz_hip.h)
         print(f"{kind} only in {'old' if name in eo else 'new'}: {name}")
-        bad += 1
+        if allow_new and name in en:
+            added += 1
+        else:
+            bad += 1
+    same = "IDENTICAL" if not added else f"IDENTICAL where both exist, {added} additions"
     print(f"{old.name} vs {new.name}: {len(set(ko) & set(kn))} kernels ({ninsn} instructions), "
-          f"{len(en)} exported names: {'IDENTICAL' if not bad else f'{bad} DIFFERENCES'}")
+          f"{len(en)} exported names: {same if not bad else f'{bad} DIFFERENCES'}")
     return 1 if bad else 0
 
 
