@@ -21,7 +21,8 @@
 // Precision: fp16 hi/lo pieces, 3 products (Wh·Xh + Wh·Xl + Wl·Xh) as in the x6 kernel's
 // f16x3 GEMM2/3.  GEMM1 takes that path when every context/data value of the workgroup's rows
 // is below 2^15; otherwise the workgroup runs GEMM1 in EXACT fp32 (v_mfma_f32_16x16x4_f32,
-// a second stage-A image of the same size).  Activation fold, select-first spline and LDS-DMA
+// a second stage-A image with the same offsets).  GEMM1's last k-step, a few real k-slots per
+// quarter, packs its three products into one MFMA's k-slots (CfgR16::CAT1).  Activation fold, select-first spline and LDS-DMA
 // ring as in coupling_x6_kernel.
 #pragma once
 #include "../../include/naz_hip.h"  // NAZ_LD_ROWSUM*
@@ -91,11 +92,26 @@ struct CfgR16 {
   static constexpr bool SPLIT3 = DQ == 2 && NO % 2 == 0 && (P + 3) / 4 <= NO / 2;
   static constexpr int NOC = SPLIT3 ? NO / 2 : NO;     // output blocks per GEMM3 stage
   static constexpr int KB3 = pick_kb(NOC, 16 * NO), NB3H = KS2 / KB3, NB3 = (SPLIT3 ? 2 : 1) * NB3H;
-  // stage A (fp16 image; the fp32 image A32 has the same size and bias/table offsets):
-  //   [HB][KS1][2][256] | bias [H] | tables [S][TBL]
-  static constexpr int A_BIAS = HB * KS1 * OT;
+  // GEMM1's last k-step holds NR1 real k-slots per quarter (the quarter's x1 dims, then whatever
+  // context is left over from the full steps).  When their three f16x3 products fit one MFMA's 8
+  // k-slots the step is CONCATENATED (CAT1): A slots [Wh | Wh | Wl | 0] against B slots
+  // [Xh | Xl | Xh | 0], one 1 KB A piece and one MFMA per block instead of two and three.
+  static constexpr int C_LAST = C > 32 * (KS1 - 1) ? C - 32 * (KS1 - 1) : 0;
+  static constexpr int NR1 = SQ + (C_LAST < 8 - SQ ? C_LAST : 8 - SQ);
+  // Only behind at least one full step (KS1 > 1): where the step is ALL of GEMM1, summing the small
+  // terms inside one MFMA beside the large one costs accuracy that shows in the training gradients
+  // of the D=8, C=0 shape, so those shapes keep the three-MFMA step.
+  static constexpr bool CAT1 = 3 * NR1 <= 8 && KS1 > 1;
+  static constexpr int PC1 = CAT1 ? 2 * KS1 - 1 : 2 * KS1;  // 1 KB A pieces per block of the fp16 image
+  static constexpr __host__ __device__ int g1_pieces(int t) { return CAT1 && t == KS1 - 1 ? 1 : 2; }
+  // stage A: bias [H] | tables [S][TBL] | pad | weights.  The fp16 image's weights are [HB][PC1][256]
+  // (A16_SIZE floats are staged), the fp32 image A32's [HB][2 KS1][256]; both images are A_SIZE
+  // apart in the layer and share the bias, table and weight offsets.
+  static constexpr int A_BIAS = 0;
   static constexpr int A_TBL = A_BIAS + H;
-  static constexpr int A_SIZE = pad(A_TBL + S * TBL);
+  static constexpr int A_W = pad(A_TBL + S * TBL);
+  static constexpr int A16_SIZE = A_W + HB * PC1 * kChunk;
+  static constexpr int A_SIZE = pad(A_W + HB * KS1 * OT);
   static constexpr int B_OFF = A_SIZE;
   static constexpr int B_BIAS = HB * KB2 * OT;
   static constexpr int B_SIZE = pad(B_BIAS + H);
@@ -106,6 +122,8 @@ struct CfgR16 {
   static constexpr int LAYER = A32_OFF + A_SIZE;
   static constexpr int NSTG = 1 + NB2 + NB3;
   static constexpr int MAXSTAGE = 2 * kX6Slot;
+  // no stage reaches the last SLOT_FREE floats of a ring slot
+  static constexpr int SLOT_FREE = kX6Slot - (A_SIZE > B_SIZE ? (A_SIZE > C_SIZE ? A_SIZE : C_SIZE) : (B_SIZE > C_SIZE ? B_SIZE : C_SIZE));
   static constexpr __host__ __device__ int stage_off(int j) {
     return j == 0 ? 0 : (j <= NB2 ? B_OFF + (j - 1) * B_SIZE : C_OFF + (j - 1 - NB2) * C_SIZE);
   }
@@ -157,7 +175,8 @@ __global__ void coupling_pack_r16_kernel(const float* __restrict__ flat, float* 
     const float* W2 = b1 + CF::N_B1;
     const float* b2 = W2 + CF::N_W2;
     const float* low = b2 + CF::N_B2;
-    // f16 chunk word: (o, t, piece, lane, pair) -> two fp16 pieces of the scaled weight
+    // f16 chunk word of GEMM2 (which = 1) / GEMM3 (2): (o, t, piece, lane, pair) -> two fp16 pieces
+    // of the scaled weight
     auto chunk_word = [&](int q, int nt, int t0, int which, int obase = 0) -> unsigned {
       const int o = q / (nt * CF::OT), r1 = q - o * nt * CF::OT;
       const int tl = r1 / CF::OT, r2 = r1 - tl * CF::OT;
@@ -168,10 +187,7 @@ __global__ void coupling_pack_r16_kernel(const float* __restrict__ flat, float* 
       for (int e2 = 0; e2 < 2; ++e2) {
         const int j = 2 * pair + e2;
         float v = 0.f;
-        if (which == 0) {
-          const int col = r16_in_col<CF>(t, qq, j);
-          v = col >= 0 ? kSigScale * W0[(16 * o + i) * (CF::C + CF::S) + col] : 0.f;
-        } else if (which == 1) {
+        if (which == 1) {
           v = -2.f * kSigScale * W1[(16 * o + i) * CF::H + r16_feat(t, qq, j)];
         } else {
           const int orow = r16_out_row<CF>(obase + o, i);
@@ -187,14 +203,35 @@ __global__ void coupling_pack_r16_kernel(const float* __restrict__ flat, float* 
     const bool a32 = off >= CF::A32_OFF;
     if (off < CF::A_SIZE || a32) {
       const int oa = a32 ? off - CF::A32_OFF : off;
-      if (oa < CF::A_BIAS) {
+      if (oa >= CF::A_W) {
+        const int ow = oa - CF::A_W;
         if (!a32) {
-          word = chunk_word(oa, CF::KS1, 0, 0);
+          // fp16 image [o][piece of PC1][lane][4 words]: pieces 2t, 2t + 1 = hi, lo of full step t;
+          // the concatenated last step is ONE piece, k-slot j of n = NR1 real slots at j and n + j
+          // (hi) and 2n + j (lo), the rest zero.  The hole behind the image stays zero.
+          const int o = ow / (CF::PC1 * kChunk), r1 = ow - o * CF::PC1 * kChunk;
+          const int pc = r1 / kChunk, u = r1 - pc * kChunk, t = pc >> 1;
+          const int lane = u >> 2, pair = u & 3, i = lane & 15, qq = lane >> 4;
+          if (o < CF::HB) {
+            for (int e2 = 0; e2 < 2; ++e2) {
+              int j = 2 * pair + e2, piece = pc & 1;
+              bool real = true;
+              if (CF::g1_pieces(t) == 1) {
+                const int seg = j / CF::NR1;
+                j -= seg * CF::NR1;
+                piece = seg == 2 ? 1 : 0;
+                real = seg < 3;
+              }
+              const int col = real ? r16_in_col<CF>(t, qq, j) : -1;
+              const float v = col >= 0 ? kSigScale * W0[(16 * o + i) * (CF::C + CF::S) + col] : 0.f;
+              word |= f16_piece_bits(v, piece) << (16 * e2);
+            }
+          }
           is_word = true;
-        } else {
+        } else if (ow < CF::HB * CF::KS1 * CF::OT) {
           // fp32 image [o][s4][lane][4]: k-step s = 4 s4 + i of v_mfma_f32_16x16x4_f32 on quarter
           // lane >> 4 carries the fp16 path's slot (t = s / 8, j = s % 8)
-          const int i4 = oa & 3, lane = (oa >> 2) & 63, rest = oa >> 8;
+          const int i4 = ow & 3, lane = (ow >> 2) & 63, rest = ow >> 8;
           const int s4 = rest % (2 * CF::KS1), o = rest / (2 * CF::KS1);
           const int s = 4 * s4 + i4;
           const int col = r16_in_col<CF>(s / 8, lane >> 4, s % 8);
@@ -241,11 +278,14 @@ __global__ void coupling_pack_r16_kernel(const float* __restrict__ flat, float* 
 
 // acc[o] += A(o, t) · B(t) over k-steps [0, KB), t outer, o inner, with each A fragment read one
 // MFMA triple ahead (untracked LDS reads with counted waits, lds_ring.h lds_read_b128_untracked):
-// for kernels with too few waves per SIMD to hide an LDS read behind other waves' work (the
-// training backward: two).  bfn(t) returns k-step t's B fragment (formed inside the loop, so the
+// hipcc's own waits expose a full LDS latency before every MFMA triple, which neither the
+// backward's two waves per SIMD nor the inference kernel's four (in lock step between stage
+// barriers) hide.  bfn(t) returns k-step t's B fragment (formed inside the loop, so the
 // lazy forms' activation VALU still lands between MFMAs).
-template <int NB, int KB, class BFn>
-NAZ_DEV void gemm_r16_pf(floatx4 (&acc)[NB], const float* __restrict__ stage, int lane, BFn&& bfn) {
+// The NB blocks accumulate into acc[OB .. OB + NB).
+template <int NB, int KB, int OB = 0, int NA, class BFn>
+NAZ_DEV void gemm_r16_pf(floatx4 (&acc)[NA], const float* __restrict__ stage, int lane, BFn&& bfn) {
+  static_assert(OB + NB <= NA, "accumulator window");
   static_assert(2 * NB * KB * 1024 <= 65536, "A fragment offsets must fit the 16-bit LDS offset");
   const unsigned ub = (unsigned)(uintptr_t)to_lds(stage) + 16u * lane;
   auto rd = [&](auto oc, auto tc) {
@@ -270,27 +310,88 @@ NAZ_DEV void gemm_r16_pf(floatx4 (&acc)[NB], const float* __restrict__ stage, in
         lds_wait<0>();
       }
       __builtin_amdgcn_sched_barrier(0);
-      acc[o] = mfma3_16(a, b, acc[o]);
+      acc[OB + o] = mfma3_16(a, b, acc[OB + o]);
     });
   });
 }
 
-// acc[o] += A(o, t) · B(t) over k-steps [0, KB) with B fragments given (PF: gemm_r16_pf)
-template <int NB, int KB, bool PF = false>
-NAZ_DEV void gemm_r16_stage(floatx4 (&acc)[NB], const float* __restrict__ stage, int lane, const Frag2 (&bf)[KB]) {
-  if constexpr (PF) {
-    gemm_r16_pf<NB, KB>(acc, stage, lane, [&](auto tc) -> Frag2 { return bf[decltype(tc)::value]; });
-    return;
+// GEMM1's B operands from this lane's input k-slots.  Full steps: the hi/lo fragments.  The
+// concatenated last step (CF::CAT1): bf[KS1 - 1].h = [xh | xl | xh | 0] over its NR1 real slots
+// (against the packer's [Wh | Wh | Wl | 0]); its .l is not used.
+template <class CF>
+NAZ_DEV void gemm1_frags(const float (&in)[CF::KS1 * 8], Frag2 (&bf)[CF::KS1]) {
+  typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+#pragma unroll
+  for (int t = 0; t < CF::KS1; ++t) {
+    float v[8];
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) v[jj] = in[8 * t + jj];
+    bf[t] = split8_f16(v);
   }
-  const u32x4* c4 = reinterpret_cast<const u32x4*>(stage);
+  if constexpr (CF::CAT1) {
+    constexpr int n = CF::NR1;
+    const u16x8 h = __builtin_bit_cast(u16x8, bf[CF::KS1 - 1].h), l = __builtin_bit_cast(u16x8, bf[CF::KS1 - 1].l);
+    u16x8 c = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-  for (int t = 0; t < KB; ++t)
-#pragma unroll
-    for (int o = 0; o < NB; ++o) {
-      const int base = ((o * KB + t) * 2) * 64 + lane;
-      const Frag2 a{__builtin_bit_cast(half8, c4[base]), __builtin_bit_cast(half8, c4[base + 64])};
-      acc[o] = mfma3_16(a, bf[t], acc[o]);
+    for (int j = 0; j < n; ++j) {
+      c[j] = h[j];
+      c[n + j] = l[j];
+      c[2 * n + j] = h[j];
     }
+    bf[CF::KS1 - 1].h = __builtin_bit_cast(half8, c);
+  }
+}
+
+// GEMM1 on the fp16 stage-A weights w ([HB][PC1] 1 KB pieces): acc[o] += A(o, t) · B(t), t outer, o
+// inner; full steps by mfma3_16, the concatenated last step by ONE MFMA on one piece.  PF: each
+// block's pieces are read one block ahead (as gemm_r16_pf).
+template <class CF, bool PF>
+NAZ_DEV void gemm1_r16(floatx4 (&acc)[CF::HB], const float* __restrict__ w, int lane, const Frag2 (&bf)[CF::KS1]) {
+  constexpr int HB = CF::HB, KS1 = CF::KS1, PC = CF::PC1;
+  if constexpr (PF) {
+    static_assert(HB * PC * 1024 <= 65536, "A fragment offsets must fit the 16-bit LDS offset");
+    const unsigned ub = (unsigned)(uintptr_t)to_lds(w) + 16u * lane;
+    half8 nh, nl = bf[0].l;  // nl: only read for two-piece steps, which load it first
+    auto rd = [&](auto oc, auto tc) {
+      constexpr int t = decltype(tc)::value, off = (decltype(oc)::value * PC + 2 * t) * 1024;
+      nh = __builtin_bit_cast(half8, lds_read_b128_untracked<off>(ub));
+      if constexpr (CF::g1_pieces(t) == 2) nl = __builtin_bit_cast(half8, lds_read_b128_untracked<off + 1024>(ub));
+    };
+    rd(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+    static_for<0, KS1>([&](auto tc) {
+      constexpr int t = decltype(tc)::value;
+      static_for<0, HB>([&](auto oc) {
+        constexpr int o = decltype(oc)::value;
+        const half8 ah = nh, al = nl;
+        if constexpr (o + 1 < HB || t + 1 < KS1) {
+          constexpr int t2 = o + 1 < HB ? t : t + 1;
+          rd(std::integral_constant<int, (o + 1 < HB ? o + 1 : 0)>{}, std::integral_constant<int, t2>{});
+          __builtin_amdgcn_sched_barrier(0);
+          lds_wait<CF::g1_pieces(t2)>();
+        } else {
+          __builtin_amdgcn_sched_barrier(0);
+          lds_wait<0>();
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (CF::g1_pieces(t) == 2) acc[o] = mfma3_16(Frag2{ah, al}, bf[t], acc[o]);
+        else acc[o] = mfma16_f16(ah, bf[t].h, acc[o]);
+      });
+    });
+  } else {
+    const u32x4* c4 = reinterpret_cast<const u32x4*>(w);
+#pragma unroll
+    for (int t = 0; t < KS1; ++t)
+#pragma unroll
+      for (int o = 0; o < HB; ++o) {
+        const int base = (o * PC + 2 * t) * 64 + lane;
+        if (CF::g1_pieces(t) == 2) {
+          const Frag2 a{__builtin_bit_cast(half8, c4[base]), __builtin_bit_cast(half8, c4[base + 64])};
+          acc[o] = mfma3_16(a, bf[t], acc[o]);
+        } else {
+          acc[o] = mfma16_f16(__builtin_bit_cast(half8, c4[base]), bf[t].h, acc[o]);
+        }
+      }
+  }
 }
 
 // k-steps [T0, T0 + KB) with each B fragment split from the activated accumulators just
@@ -335,7 +436,7 @@ NAZ_DEV void gemm_r16_lazy(floatx4 (&acc)[NB], const float* __restrict__ stage, 
 // GEMM3 stage s: k-steps [T0, T0 + KB3) of output blocks [OB, OB + NOC) (OB = half · NOC).
 // Half 0 forms each k-step's B fragment from the GEMM2 accumulators (ACT: activated here) and
 // keeps it in f3; half 1 reads f3.  Bias from the stage's bias block at the half's first stage.
-template <class CF, int s, bool ACT, int NX>
+template <class CF, int s, bool ACT, bool PF = false, int NX>
 NAZ_DEV void gemm3_stage(floatx4 (&acc)[CF::NO], const float* __restrict__ cur, int lane, int q, floatx4 (&x)[NX],
                          Frag2 (&f3)[CF::KS2]) {
   constexpr int h = s / CF::NB3H, s2 = s % CF::NB3H, T0 = s2 * CF::KB3, OB = h * CF::NOC;
@@ -347,9 +448,9 @@ NAZ_DEV void gemm3_stage(floatx4 (&acc)[CF::NO], const float* __restrict__ cur, 
       acc[OB + o] = floatx4{bv.x, bv.y, bv.z, bv.w};
     }
   }
-  const u32x4* c4 = reinterpret_cast<const u32x4*>(cur);
-#pragma unroll
-  for (int t = 0; t < CF::KB3; ++t) {
+  // k-step T0 + t's B fragment: formed (and kept in f3) by half 0, read back by half 1
+  auto bfrag = [&](auto tc) -> Frag2 {
+    constexpr int t = decltype(tc)::value;
     if constexpr (h == 0) {
       float v[8];
 #pragma unroll
@@ -360,13 +461,23 @@ NAZ_DEV void gemm3_stage(floatx4 (&acc)[CF::NO], const float* __restrict__ cur, 
       }
       f3[T0 + t] = split8_f16(v);
     }
+    return f3[T0 + t];
+  };
+  if constexpr (PF) {
+    gemm_r16_pf<CF::NOC, CF::KB3, OB>(acc, cur, lane, bfrag);
+    return;
+  }
+  const u32x4* c4 = reinterpret_cast<const u32x4*>(cur);
+  static_for<0, CF::KB3>([&](auto tc) {
+    constexpr int t = decltype(tc)::value;
+    const Frag2 b = bfrag(tc);
 #pragma unroll
     for (int o = 0; o < CF::NOC; ++o) {
       const int base = ((o * CF::KB3 + t) * 2) * 64 + lane;
       const Frag2 a{__builtin_bit_cast(half8, c4[base]), __builtin_bit_cast(half8, c4[base + 64])};
-      acc[OB + o] = mfma3_16(a, f3[T0 + t], acc[OB + o]);
+      acc[OB + o] = mfma3_16(a, b, acc[OB + o]);
     }
-  }
+  });
 }
 
 // Training forward (VAR = 1, coupling_train.h): the log_prob walk of the NLL step with every
@@ -374,7 +485,9 @@ NAZ_DEV void gemm3_stage(floatx4 (&acc)[CF::NO], const float* __restrict__ cur, 
 // to recompute from.  Its math is the fused inference kernel's own (sigmoid-fold activation,
 // select-first spline on hardware transcendentals, table lower spline), so the NLL step's loss is
 // the log_prob the metric kernel computes.
-// Waves per SIMD: 4 for every VAR (128 VGPRs, 12 B of scratch in the training forward at config 3).
+// Waves per SIMD: 4 for every VAR (config 3: 128 VGPRs and no scratch in the log_prob, training
+// forward and one-layer inverse instances; 12 B, outside the layer loop, in the sample direction).
+// tests/test_r16_resources.py holds the log_prob instance to that.
 template <class CF, bool DIR_INV, int VAR = 0>
 __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
     const float* __restrict__ packed, int L, const float* __restrict__ x, int64_t ldx,
@@ -389,7 +502,24 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int q = lane >> 4;
-  const int64_t row = (int64_t)blockIdx.x * kR16Rows + wave * 16 + (lane & 15);
+  // thread index behind a compiler barrier: what is derived from it is formed at the use, not hoisted
+  auto tid_now = [&]() {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+  };
+  auto row_of = [&](int t) { return (int64_t)blockIdx.x * kR16Rows + (t >> 6) * 16 + (t & 15); };
+  struct Where {
+    int64_t row;
+    bool valid;
+    int q;
+  };
+  auto where = [&]() {
+    const int t = tid_now();
+    const int64_t r = row_of(t);
+    return Where{r, r < B, (t >> 4) & 3};
+  };
+  const int64_t row = row_of(threadIdx.x);
   const bool valid = row < B;
   const int64_t crow = valid ? row : 0;
 
@@ -416,6 +546,13 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
       logjac -= sl;
     }
   }
+  // The bounding transform's log-Jacobian is needed again only after the last layer: where the ring
+  // slots have room behind their largest stage it waits there (each thread's own word of slot 0's
+  // tail, which no LDS-DMA writes), not in a register held across the layer loop.
+  constexpr bool kParkLogjac = DIR_INV && VAR != 2 && CF::SLOT_FREE >= kR16Rows * 4;
+  if constexpr (kParkLogjac) {
+    if (low != nullptr) slot0[kX6Slot - kR16Rows * 4 + threadIdx.x] = logjac;
+  }
 
   // GEMM1 precision path of this workgroup (see the file comment); reduced through ring slot 1
   bool ok = bound < kG1F16Limit;
@@ -440,10 +577,14 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
     ok = all_ok;
   }
   const bool g1f16 = ok;
-  const int a_off = g1f16 ? 0 : CF::A32_OFF;
 
   const RingSrc ring{packed};
-  stage_issue<CF::A_SIZE, kR16Waves>(slot0, ring, (DIR_INV ? (L - 1) : 0) * CF::LAYER + a_off);
+  // stage A of layer l: only what the workgroup's image holds (g1f16 is workgroup-uniform)
+  auto issue_a = [&](float* dst, int l) {
+    if (g1f16) stage_issue<CF::A16_SIZE, kR16Waves>(dst, ring, l * CF::LAYER);
+    else stage_issue<CF::A_SIZE, kR16Waves>(dst, ring, l * CF::LAYER + CF::A32_OFF);
+  };
+  issue_a(slot0, DIR_INV ? (L - 1) : 0);
 
   const RqsConsts<CF::K, DIR_INV> rc(bound);
   // GEMM1's context k-slots of this lane, loaded for layer li + 1 before layer li's upper spline
@@ -451,14 +592,20 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
   // LDS-DMA (as when it sits in stage A) can only be waited for together with that DMA, so
   // stage A would stall on stage B's weights (3 % of the kernel, same-box A/B).  Issued before
   // the stage-A barrier, the barrier's vmcnt(0) covers them with the stage-A weights.
+  // The row's address is re-derived from the thread index at each use (tid_now): as 64-bit per-row
+  // pointers kept across the layer loop, the context row and the output row were what the
+  // prefetched GEMM stages' larger live set pushed to scratch.
   float cpre[CF::KS1 * 8];
   auto load_ctx = [&]() {
+    const int t_ = tid_now(), q_ = (t_ >> 4) & 3;
+    const int64_t r_ = row_of(t_);
+    const float* cp = ctx + (r_ < B ? r_ : 0) * ldc;
 #pragma unroll
     for (int t = 0; t < CF::KS1; ++t)
 #pragma unroll
       for (int jj = 0; jj < 8; ++jj) {
-        const int col = r16_in_col<CF>(t, q, jj);
-        cpre[8 * t + jj] = (col >= 0 && col < CF::C) ? ctx[crow * ldc + col] : 0.f;
+        const int col = r16_in_col<CF>(t, q_, jj);
+        cpre[8 * t + jj] = (col >= 0 && col < CF::C) ? cp[col] : 0.f;
       }
   };
   load_ctx();
@@ -466,12 +613,13 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
   for (int li = 0; li < L; ++li) {
     const int l = DIR_INV ? (L - 1 - li) : li;
     if constexpr (VAR == 1) {  // layer l's input state P[l + 1]
-      if (valid) {
-        float* st = states + ((int64_t)(l + 1) * B + row) * CF::D;
+      const Where w = where();
+      if (w.valid) {
+        float* st = states + ((int64_t)(l + 1) * B + w.row) * CF::D;
 #pragma unroll
-        for (int u = 0; u < CF::SQ; ++u) st[q * CF::SQ + u] = zl[u];
+        for (int u = 0; u < CF::SQ; ++u) st[w.q * CF::SQ + u] = zl[u];
 #pragma unroll
-        for (int u = 0; u < CF::DQ; ++u) st[CF::S + q * CF::DQ + u] = zu[u];
+        for (int u = 0; u < CF::DQ; ++u) st[CF::S + w.q * CF::DQ + u] = zu[u];
       }
     }
     floatx4 acc1[CF::HB], acc2[CF::HB], acc3[CF::NO];
@@ -504,9 +652,10 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
       if constexpr (j + 1 < CF::NSTG) {
         stage_issue<CF::stage_size(j + 1), kR16Waves>(nxt, ring, l * CF::LAYER + CF::stage_off(j + 1));
       } else {
-        if (li + 1 < L) stage_issue<CF::A_SIZE, kR16Waves>(nxt, ring, (DIR_INV ? (l - 1) : (l + 1)) * CF::LAYER + a_off);
+        if (li + 1 < L) issue_a(nxt, DIR_INV ? (l - 1) : (l + 1));
       }
       ++g;
+      const int lane = tid_now() & 63;  // the stage's LDS lane offset, formed here (not kept across stages)
 
       if constexpr (j == 0) {
         // ---------------- stage A: lower spline (inverse), GEMM1 over [ctx | x1]
@@ -539,19 +688,13 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
         }
         if (g1f16) {
           Frag2 bf[CF::KS1];
-#pragma unroll
-          for (int t = 0; t < CF::KS1; ++t) {
-            float v[8];
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) v[jj] = in[8 * t + jj];
-            bf[t] = split8_f16(v);
-          }
+          gemm1_frags<CF>(in, bf);
           __builtin_amdgcn_s_setprio(1);
-          gemm_r16_stage<CF::HB, CF::KS1>(acc1, cur, lane, bf);
+          gemm1_r16<CF, true>(acc1, cur + CF::A_W, lane, bf);
           __builtin_amdgcn_s_setprio(0);
         } else {
           // exact fp32: 8 KS1 k-steps of 4; k-step s on this lane = slot (s / 8, s % 8)
-          const float4* p4 = reinterpret_cast<const float4*>(cur);
+          const float4* p4 = reinterpret_cast<const float4*>(cur + CF::A_W);
 #pragma unroll
           for (int s4 = 0; s4 < 2 * CF::KS1; ++s4)
 #pragma unroll
@@ -583,14 +726,14 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
           }
         }
         __builtin_amdgcn_s_setprio(1);
-        gemm_r16_lazy<CF::HB, CF::KB2, T0, true>(acc2, cur, lane, acc1);  // activated per k-step inside
+        gemm_r16_lazy<CF::HB, CF::KB2, T0, true, CF::HB, true>(acc2, cur, lane, acc1);  // activated per k-step inside
         __builtin_amdgcn_s_setprio(0);
       } else {
         // ---------------- stage C_s: GEMM3 (two halves of output blocks when SPLIT3)
         constexpr int s = j - 1 - CF::NB2;
         constexpr bool kHost = CF::SPLIT3 && s == CF::NB3H;  // first stage of half 1: dim 0's spline
         if constexpr (!kHost) __builtin_amdgcn_s_setprio(1);
-        gemm3_stage<CF, s, true>(acc3, cur, lane, q, acc2, f3);
+        gemm3_stage<CF, s, true, true>(acc3, cur, lane, q, acc2, f3);
         if constexpr (!kHost) __builtin_amdgcn_s_setprio(0);
         // dim 0's spline in the stage that issues half 1's MFMAs (the compiler still issues the
         // MFMAs first: measured the same as without SPLIT3, also with sched_group_barrier pins)
@@ -612,30 +755,31 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
     }
 #endif
   }
+  const Where w = where();  // re-derived after the layer loop (see load_ctx)
   if constexpr (VAR == 1) {  // P[0] = z
-    if (valid) {
-      float* st = states + row * CF::D;
+    if (w.valid) {
+      float* st = states + w.row * CF::D;
 #pragma unroll
-      for (int u = 0; u < CF::SQ; ++u) st[q * CF::SQ + u] = zl[u];
+      for (int u = 0; u < CF::SQ; ++u) st[w.q * CF::SQ + u] = zl[u];
 #pragma unroll
-      for (int u = 0; u < CF::DQ; ++u) st[CF::S + q * CF::DQ + u] = zu[u];
+      for (int u = 0; u < CF::DQ; ++u) st[CF::S + w.q * CF::DQ + u] = zu[u];
     }
   }
 
   if constexpr (VAR == 2) {
-    if (valid) {
+    if (w.valid) {
 #pragma unroll
-      for (int u = 0; u < CF::SQ; ++u) yout[row * ldy + q * CF::SQ + u] = zl[u];
+      for (int u = 0; u < CF::SQ; ++u) yout[w.row * ldy + w.q * CF::SQ + u] = zl[u];
 #pragma unroll
-      for (int u = 0; u < CF::DQ; ++u) yout[row * ldy + CF::S + q * CF::DQ + u] = zu[u];
+      for (int u = 0; u < CF::DQ; ++u) yout[w.row * ldy + CF::S + w.q * CF::DQ + u] = zu[u];
     }
     float v = ldsum;
     v += __shfl_xor(v, 16);
     v += __shfl_xor(v, 32);
-    if (q == 0 && valid) {
-      if (layer_ld_mode == NAZ_LD_ROWSUM_ADD) out_lp[row] += v;
-      else if (layer_ld_mode == NAZ_LD_ROWSUM_SUB) out_lp[row] -= v;
-      else out_lp[row] = v;
+    if (w.q == 0 && w.valid) {
+      if (layer_ld_mode == NAZ_LD_ROWSUM_ADD) out_lp[w.row] += v;
+      else if (layer_ld_mode == NAZ_LD_ROWSUM_SUB) out_lp[w.row] -= v;
+      else out_lp[w.row] = v;
     }
   } else if constexpr (DIR_INV) {
     constexpr float kLogSqrt2Pi = 0.91893853320467274178f;
@@ -644,34 +788,35 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
     for (int u = 0; u < CF::SQ; ++u) base += -(zl[u] * zl[u]) / 2.f - kLogSqrt2Pi;
 #pragma unroll
     for (int u = 0; u < CF::DQ; ++u) base += -(zu[u] * zu[u]) / 2.f - kLogSqrt2Pi;
+    if constexpr (kParkLogjac) logjac = low != nullptr ? slot0[kX6Slot - kR16Rows * 4 + tid_now()] : 0.f;
     float v = base - ldsum + logjac;
     v += __shfl_xor(v, 16);
     v += __shfl_xor(v, 32);
-    if (q == 0 && valid) out_lp[row] = v;
+    if (w.q == 0 && w.valid) out_lp[w.row] = v;
   } else {
     if (low != nullptr) {
 #pragma unroll
       for (int u = 0; u < CF::SQ; ++u) {
-        const int d = q * CF::SQ + u;
+        const int d = w.q * CF::SQ + u;
         zl[u] = (1.f / (1.f + expf(-zl[u]))) * (high[d] - low[d]) + low[d];
       }
 #pragma unroll
       for (int u = 0; u < CF::DQ; ++u) {
-        const int d = CF::S + q * CF::DQ + u;
+        const int d = CF::S + w.q * CF::DQ + u;
         zu[u] = (1.f / (1.f + expf(-zu[u]))) * (high[d] - low[d]) + low[d];
       }
     }
-    if (valid) {
+    if (w.valid) {
 #pragma unroll
-      for (int u = 0; u < CF::SQ; ++u) yout[row * ldy + q * CF::SQ + u] = zl[u];
+      for (int u = 0; u < CF::SQ; ++u) yout[w.row * ldy + w.q * CF::SQ + u] = zl[u];
 #pragma unroll
-      for (int u = 0; u < CF::DQ; ++u) yout[row * ldy + CF::S + q * CF::DQ + u] = zu[u];
+      for (int u = 0; u < CF::DQ; ++u) yout[w.row * ldy + CF::S + w.q * CF::DQ + u] = zu[u];
     }
     if (out_lp != nullptr) {
       float v = ldsum;
       v += __shfl_xor(v, 16);
       v += __shfl_xor(v, 32);
-      if (q == 0 && valid) out_lp[row] = v;
+      if (w.q == 0 && w.valid) out_lp[w.row] = v;
     }
   }
 }

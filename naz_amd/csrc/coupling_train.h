@@ -157,7 +157,8 @@ struct BwdOut {
 // VALU phases (activations, spline VJPs) overlap the other's MFMA phases; the waves of ONE
 // workgroup run the same phase between stage barriers.
 constexpr int kBwdWaves = 4;
-// The backward's GEMMs read their A fragments one MFMA triple ahead (gemm_r16_pf, PF = true below):
+// The backward's GEMMs read their A fragments one MFMA triple ahead (gemm_r16_pf, PF = true below;
+// GEMM3's recompute, gemm3_stage, is left on tracked reads):
 // two waves per SIMD do not hide the LDS latency hipcc's lgkmcnt(0) waits expose.
 // The operands nothing in this kernel re-reads (dPre3, dPre2, dPre1, X0) are plain stores: the
 // non-temporal form was A/B'd and not kept.
@@ -202,7 +203,7 @@ __global__ void __launch_bounds__(kBwdWaves * 64, 2) coupling_bwd_r16_kernel(
 
   int g = 0;  // global stage counter: stage g lives in slot (g & 1)
   int64_t tile = blockIdx.x;
-  if (tile < ntiles) stage_issue<CF::A_SIZE, kBwdWaves>(slot0, lp);  // A32 image never used: f16x3 path only
+  if (tile < ntiles) stage_issue<CF::A16_SIZE, kBwdWaves>(slot0, lp);  // A32 image never used: f16x3 path only
   for (; tile < ntiles; tile += gridDim.x) {
     const int64_t row = tile * ROWS + wave * 16 + (lane & 15);
     const bool valid = row < B;
@@ -278,7 +279,7 @@ __global__ void __launch_bounds__(kBwdWaves * 64, 2) coupling_bwd_r16_kernel(
       } else if constexpr (j + 1 < NSTG) {
         stage_issue<BW::stage_size(j + 1 - NSTG_F), kBwdWaves>(nxt, stage_src(j + 1));
       } else {
-        if (has_next) stage_issue<CF::A_SIZE, kBwdWaves>(nxt, lp);
+        if (has_next) stage_issue<CF::A16_SIZE, kBwdWaves>(nxt, lp);
       }
       ++g;
 
@@ -318,14 +319,8 @@ __global__ void __launch_bounds__(kBwdWaves * 64, 2) coupling_bwd_r16_kernel(
         {  // f16x3 GEMM1: the caller guarantees |x|, |ctx| < 2^15 (so the training forward took
            // the same path; states stay within max(|x|, bound))
           Frag2 bf[CF::KS1];
-#pragma unroll
-          for (int t = 0; t < CF::KS1; ++t) {
-            float v[8];
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) v[jj] = in[8 * t + jj];
-            bf[t] = split8_f16(v);
-          }
-          gemm_r16_stage<CF::HB, CF::KS1, true>(h1, cur, lane, bf);
+          gemm1_frags<CF>(in, bf);
+          gemm1_r16<CF, true>(h1, cur + CF::A_W, lane, bf);
         }
         // activation -> natural tanh (stored) ; the next GEMM consumes -tanh/2 (the fold)
 #pragma unroll
