@@ -413,17 +413,23 @@ int naz_gemm_jvp_bwd(const float* A, int64_t lda, int K, const float* W, int64_t
  * driven by NormalizingFlow.log_prob (flow.py:45-79), over L layers of
  * ConditionalAutoRegressiveNN(C + D -> H x n_hidden -> D P, tanh) conditioners: ONE launch, every MADE
  * hidden unit computed once (in the pass of its mask degree), f16x3 MFMA, the select-first inverse
- * spline (P = 3K - 1) or the clamped affine inverse (P = 2: mean, log_scale in [-5, 3]) per pass.
+ * spline (P = 3K - 1; 4K - 1 for the linear order) or the clamped affine inverse (P = 2: mean, log_scale in [-5, 3]) per pass.
  * The hidden-unit degrees the kernel assumes are pyro's (naz_ar_flow_degrees); the caller checks
  * its masks against them. */
 #define NAZ_AR_SPLINE 0 /* ConditionalSplineAutoregressive, quadratic RQ spline (naz nsa) */
 #define NAZ_AR_AFFINE 1 /* ConditionalAffineAutoregressive, stable=False (naz maf) */
+/* ConditionalSplineAutoregressive with order="linear" (pyro's default): the rational-linear spline,
+ * P = 4K - 1 (widths, heights, slopes, λ per bin).  log_prob and sample of D=4 | C=2 and D=8 | C=0 at
+ * H=[128,128], K=8; the images differ from NAZ_AR_SPLINE's (another layout tag: one kind's
+ * descriptor refuses the other's image); no pass-0-constants form (naz_ar_flow_pass0_floats < 0), no
+ * fused backward (naz_spline_ar_flow_bwd_* and naz_spline_ar_flow_log_prob_train reject it). */
+#define NAZ_AR_SPLINE_LINEAR 2
 typedef struct naz_ar_desc {
   int D, C, H, K, L; /* data dim, context dim, hidden width, bins (spline only), layers */
   int act;           /* NAZ_ACT_TANH */
   float bound;       /* spline box half-width (spline only) */
   int n_hidden;      /* hidden layers, all of width H */
-  int kind;          /* NAZ_AR_SPLINE | NAZ_AR_AFFINE */
+  int kind;          /* NAZ_AR_SPLINE | NAZ_AR_AFFINE | NAZ_AR_SPLINE_LINEAR */
   int flags;         /* NAZ_AR_CLIP_ZERO_GRAD (affine backward only); 0 = pyro semantics */
   int reserved[5];
 } naz_ar_desc;

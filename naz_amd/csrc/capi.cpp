@@ -100,7 +100,7 @@ static ImgSpec spec_ar(const naz_ar_desc* d, uint32_t kind) {
                                          : ar_flow_bwd_packed_bytes(d);
   return {kind,
           layout_tag(kind, {(uint32_t)d->D, (uint32_t)d->C, (uint32_t)d->H, (uint32_t)d->K, (uint32_t)d->act,
-                            d->kind == NAZ_AR_SPLINE ? fbits(d->bound) : 0u, (uint32_t)d->n_hidden,
+                            d->kind != NAZ_AR_AFFINE ? fbits(d->bound) : 0u, (uint32_t)d->n_hidden,
                             (uint32_t)d->kind}),
           d->L, b};
 }

@@ -1,5 +1,6 @@
 // Host dispatch of the fused autoregressive flows (naz "nsa" / "maf"): the ar_flow_* entry points
 // over made_ar_r16.h (log_prob and sample) and made_ar_wide.h (the wide production MAFs).
+#include "made_ar_linear.h"
 #include "made_ar_r16.h"
 #include "made_ar_wide.h"
 #include "naz_internal.h"
@@ -8,6 +9,10 @@
 #include <type_traits>
 
 namespace naz {
+
+// the linear-order instances' kernels are compiled in made_ar_linear.hip
+NAZ_AR_LIN_KERNELS(extern, ArLin4x2)
+NAZ_AR_LIN_KERNELS(extern, ArLin8x0)
 
 // ---- forward (sample) direction, shared by AROps and AROpsW: made_ar_fwd_kernel over CfgARF<G>'s
 // per-layer image
@@ -72,6 +77,7 @@ struct AROps : ARFwdOps<CF> {
                       int64_t P = 1, int64_t spk = 0, int64_t sx = 0, int64_t slp = 0, int c0mode = 0,
                       float* states = nullptr, void* = nullptr, int64_t = 0) {
     static_assert(2 * CF::STG * 4 <= 160 * 1024, "two weight stages exceed the LDS");
+    if (c0mode && CF::LINEAR) return set_error("naz_ar_flow: the linear-order spline has no pass-0 constants form");
     if (B == 0 || L == 0 || P == 0) return 0;
     if (P > 65535) return set_error("naz_ar_flow_log_prob_batched: at most 65535 draws per call");
     const int64_t rows = 16 * CF::NW, grid = (B + rows - 1) / rows;
@@ -81,10 +87,12 @@ struct AROps : ARFwdOps<CF> {
     return check_launch("made_ar_r16_kernel");
   }
   static int64_t workspace_bytes(int64_t, int64_t) { return 0; }  // every intermediate stays on chip
-  static int64_t pass0_floats() { return CF::C0; }
+  static int64_t pass0_floats() { return CF::LINEAR ? -1 : CF::C0; }
   static int pack_device(const float* flat, int64_t sflat, const int* perm, float* packed, int64_t spk, int L,
                          int64_t P, hipStream_t s, const float* c0 = nullptr, int64_t sc0 = 0,
                          const float* mask = nullptr) {
+    if (c0 != nullptr && CF::LINEAR)
+      return set_error("naz_ar_flow_pack: the linear-order spline has no pass-0 constants form");
     if (L == 0 || P == 0) return 0;
     if (P > 65535 || L > 65535) return set_error("naz_ar_flow_pack: at most 65535 draws / layers per call");
     const dim3 grid((unsigned)((CF::LAYER + 255) / 256), (unsigned)L, (unsigned)P);
@@ -173,6 +181,14 @@ static int ar_dispatch(const naz_ar_desc* d, F&& f) {
     if (d->D == 16 && d->C == 0) return f(AROps<CfgAR<16, 0, 128, 8>>{});
     if (d->D == 8 && d->C == 0) return f(AROps<CfgAR<8, 0, 128, 8>>{});
     if (d->D == 4 && d->C == 2) return f(AROps<CfgAR<4, 2, 128, 8>>{});  // naz nsa bench shape
+    return -2;
+  }
+  if (d->kind == NAZ_AR_SPLINE_LINEAR) {
+    // order="linear" (pyro's default): naz's own nsa shape and the no-context layout; log_prob and
+    // sample only (the training step and the D = 16 shapes keep the per-kernel chain)
+    if (d->K != 8 || d->H != 128 || d->n_hidden != 2 || !(d->bound > 0.f)) return -2;
+    if (d->D == 8 && d->C == 0) return f(AROps<ArLin8x0>{});
+    if (d->D == 4 && d->C == 2) return f(AROps<ArLin4x2>{});
     return -2;
   }
   if (d->kind == NAZ_AR_AFFINE) {

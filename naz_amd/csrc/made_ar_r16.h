@@ -29,6 +29,7 @@
 // dim index d_p addresses it through M0-relative moves).
 #pragma once
 #include "coupling_r16.h"
+#include "rls_bin.h"
 
 namespace naz {
 
@@ -55,9 +56,15 @@ constexpr int kARInvWaves = 12;  // the inverse's workgroup where three waves pe
 // (other table) exchanges, then evaluates the bin — the same arithmetic as rqs_select<K, true>
 // (same knot formula, prefix sums in the same order), so the map and log-det agree with it to
 // the rounding of the split prefix sums.  All four lanes of a row return the same value.
+// inv_quad_bin is the search and assembly (the selected bin, the same on all four lanes), shared
+// with the rational-linear spline below.
+struct InvQuadBin {
+  float co0, co1, cs0, cs1, d0, d1;  // x (width) knots, y (height) knots, knot slopes
+  int idx;
+};
 template <int K>
-NAZ_DEV float rqs_select_inv_quad(const floatx4& b0, const floatx4& b1, int q, float y, float bound,
-                                  const RqsConsts<K, true>& rc, float& ld) {
+NAZ_DEV InvQuadBin inv_quad_bin(const floatx4& b0, const floatx4& b1, int q, float y, float bound,
+                                const RqsConsts<K, true>& rc) {
   static_assert(K == 8, "the quarter layout holds 8 bins: two half-tables of 4 per table");
   constexpr float kL2E = 1.44269504088896341f;
   const int qh = q & 1;          // half-table: knots 1-4 (0) or 5-8 (1)
@@ -125,17 +132,127 @@ NAZ_DEV float rqs_select_inv_quad(const floatx4& b0, const floatx4& b1, int q, f
   const float udl = pick_ud(first ? 0 : idx - 1), udh = pick_ud(last ? 0 : idx);
   const float d0 = first ? 1.f - kMinDerivative : kMinDerivative + softplus<true>(udl);
   const float d1 = last ? 1.f - kMinDerivative : kMinDerivative + softplus<true>(udh);
+  return InvQuadBin{co0, co1, cs0, cs1, d0, d1, idx};
+}
+
+template <int K>
+NAZ_DEV float rqs_select_inv_quad(const floatx4& b0, const floatx4& b1, int q, float y, float bound,
+                                  const RqsConsts<K, true>& rc, float& ld) {
+  const InvQuadBin s = inv_quad_bin<K>(b0, b1, q, y, bound, rc);
   float lb;
-  const float x = rqs_bin<true>(y, co0, co1 - co0, cs0, cs1 - cs0, d0, d1, lb);
+  const float x = rqs_bin<true>(y, s.co0, s.co1 - s.co0, s.cs0, s.cs1 - s.cs0, s.d0, s.d1, lb);
   const bool inside = y >= -bound && y <= bound;
   ld = inside ? lb : 0.f;
   return inside ? x : y;
 }
 
+// The rational-linear spline (order="linear", rls_bin.h) on the same quarter layout.  The dim's
+// 4K - 1 = 31 parameters still fill two output blocks (CfgARLin::slot): block 1's quarters 2 | 3,
+// idle for the quadratic spline, hold the unnormalised λ of bins 0-3 | 4-7.  The bin is
+// inv_quad_bin's; its λ is register idx & 3 of the λ quarter idx >> 2, shared to the row's other
+// three lanes by the slope parameters' xor-16 / xor-32 exchanges (on all lanes, outside any
+// select); then the inverse rational-linear map, on the clamped input so that every intermediate
+// is finite (rls_eval's form).  Tails and NaN pass through by selection with ld = 0.
+template <int K>
+NAZ_DEV float rls_select_inv_quad(const floatx4& b0, const floatx4& b1, int q, float y, float bound,
+                                  const RqsConsts<K, true>& rc, float& ld) {
+  const bool inside = y >= -bound && y <= bound;   // false for NaN
+  const float v = fminf(fmaxf(y, -bound), bound);  // fmaxf(NaN, -B) = -B
+  const InvQuadBin s = inv_quad_bin<K>(b0, b1, q, v, bound, rc);
+  const int j = s.idx & 3;
+  const float mine = j == 0 ? b1[0] : (j == 1 ? b1[1] : (j == 2 ? b1[2] : b1[3]));
+  const float theirs = __shfl_xor(mine, 16);
+  const float pair = ((s.idx >> 2) == (q & 1)) ? mine : theirs;  // λ of bin idx on quarters 2 and 3
+  const float other = __shfl_xor(pair, 32);
+  const RlsBin b{s.co0, s.co1, s.cs0, s.cs1, s.d0, s.d1, q >= 2 ? pair : other, s.idx};
+  float lb;
+  const float x = rls_bin<true, Math<true>, float>(b, v, lb);
+  ld = inside ? lb : 0.f;
+  return inside ? x : y;
+}
+
+// The forward rational-linear spline of one dim from its parameters in registers (the sampler:
+// every lane owns a dim).  Select-first like rls_pick_select, but the searched (x) table's prefix
+// sums, knots and θ = (x − x_k) / W are formed in DOUBLE from float softmax numerators: θ's error is
+// the knots' absolute error (a few 1e-7 in float, near ±B) over widths down to 2B·1e-3, and the
+// log-det multiplies it by up to (wc − 1) / den.  With rls_pick_select + rls_bin in float the
+// summed log-det of the D = 8 flow had 20 of 1500 rows above 1e-5 where the float32 reference has
+// 3 (the standalone kernels: 12); the map itself on IEEE arithmetic changed nothing, the whole
+// evaluator in double left 0 at 1.45x the sampler's time, this form leaves 1 at 1.13x (DESIGN
+// §4.12).  The height table needs relative accuracy only: the bin's height comes from its own
+// numerator, A_h·e_idx + 2B·m, not from a difference of two knots.  The bin's slopes and λ are
+// selected in the search loop with the knots.  Tails and NaN pass through by selection, ld = 0.
+template <int K>
+NAZ_DEV float rls_select_fwd(const float* uw, const float* uh, const float* ud, const float* ul, float x,
+                             float bound, const RqsConsts<K, false>& rc, float& ld) {
+  constexpr double kMin = 1e-3, kEps = 1e-6;  // pyro's min_bin_width, search eps (rls_pick_double's)
+  const bool inside = x >= -bound && x <= bound;   // false for NaN
+  const float v = fminf(fmaxf(x, -bound), bound);  // fmaxf(NaN, -B) = -B
+  float mw = uw[0], mh = uh[0];
+#pragma unroll
+  for (int k = 1; k < K; ++k) {
+    mw = fmaxf(mw, uw[k]);
+    mh = fmaxf(mh, uh[k]);
+  }
+  double Ew[K + 1];
+  float eh[K], Eh[K + 1];
+  Ew[0] = 0.0;
+  Eh[0] = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    Ew[k + 1] = Ew[k] + (double)expf(uw[k] - mw);
+    eh[k] = expf(uh[k] - mh);
+    Eh[k + 1] = Eh[k] + eh[k];
+  }
+  const double bd = (double)bound, vd = (double)v;
+  const double m2 = 2.0 * bd * kMin;
+  const double As = 2.0 * bd * (1.0 - kMin * K) / Ew[K];
+  double s0 = 0.0, s1 = Ew[1];
+  float o0 = 0.f, eo = eh[0], udl = ud[0], udh = ud[0], u = ul[0];
+  int idx = 0;
+#pragma unroll
+  for (int k = 1; k < K; ++k) {
+    const bool s = vd >= As * Ew[k] + m2 * k - bd + kEps;
+    s0 = s ? Ew[k] : s0;
+    s1 = s ? Ew[k + 1] : s1;
+    o0 = s ? Eh[k] : o0;
+    eo = s ? eh[k] : eo;
+    udl = s ? ud[k - 1] : udl;
+    if (k < K - 1) udh = s ? ud[k] : udh;
+    u = s ? ul[k] : u;
+    idx += s ? 1 : 0;
+  }
+  const bool first = idx == 0, last = idx == K - 1;
+  const double cw0 = first ? -bd : As * s0 + m2 * idx - bd;
+  const double cw1 = last ? bd : As * s1 + m2 * (idx + 1) - bd;
+  const double Wd = cw1 - cw0;
+  const float th = (float)((vd - cw0) / Wd), om = (float)((cw1 - vd) / Wd), W = (float)Wd;
+  const float Ah = rc.cA / Eh[K];
+  const float ch0 = __builtin_fmaf(Ah, o0, __builtin_fmaf(rc.mo, (float)idx, rc.nb));
+  const float H = last ? bound - ch0 : __builtin_fmaf(Ah, eo, rc.mo);
+  const float d0 = first ? 1.f - kMinDerivative : kMinDerivative + softplus<false>(udl);
+  const float d1 = last ? 1.f - kMinDerivative : kMinDerivative + softplus<false>(udh);
+  // rls_bin's forward map (rls_bin.h) on θ, 1 − θ, W and H as formed above
+  const float lam = (1.f - 2.f * kMinLambda) / (1.f + expf(-u)) + kMinLambda, oml = 1.f - lam;
+  const float wb = sqrtf(d0 / d1);
+  const float wc = (lam * d0 + oml * wb * d1) * W / H;
+  const float Hs = H / (oml + lam * wb);
+  const float ca = lam * wb * Hs, cb = oml * Hs;
+  const bool left = th <= lam;
+  const float den = left ? (lam - th) + wc * th : wc * om + wb * (th - lam);
+  const float q = (left ? wc * ca * th : wc * cb * om) / den;
+  const float y = left ? ch0 + q : (ch0 + H) - q;
+  const float lb = logf((left ? lam * ca : wb * oml * cb) * wc / W / (den * den));
+  ld = inside ? lb : 0.f;
+  return inside ? y : x;
+}
+
+#define NAZ_CFG_INLINE __attribute__((always_inline))
 template <int D_, int C_, int H_, int K_, int NHID_ = 2, bool AFFINE_ = false>
 struct CfgAR {
   static constexpr int D = D_, C = C_, H = H_, K = K_, NHID = NHID_;
   static constexpr bool AFFINE = AFFINE_;
+  static constexpr bool LINEAR = false;                 // the spline's order (CfgARLin below)
   static constexpr int P = AFFINE ? 2 : 3 * K - 1;      // ARN outputs per dim
   static constexpr int HP = (H + 31) / 32 * 32;         // padded hidden width
   static constexpr int HB = HP / 16, KSH = HP / 32;     // hidden 16-unit blocks, 32-k steps over them
@@ -143,6 +260,14 @@ struct CfgAR {
   static constexpr int KI = KC + 1;                     // + one k-step over x (D <= 32)
   static constexpr int NOB = (P + 15) / 16;             // output blocks (params of one dim)
   static constexpr int OT = 2 * kChunk;                 // floats per (block, k-step): hi + lo
+  // Output row of a dim's parameter pi (pyro's param_dims order) in the inverse image's output
+  // blocks: row r = block r >> 4, quarter (r & 15) >> 2, register r & 3 of the 16-row MFMA result.
+  // Both packers place the ARN's output rows through these three (row_used / row_param: slot's
+  // inverse); CfgARLin redefines them.  (Inlined before the optimizer's cost model sees a call:
+  // the packer kernels keep the code they had with the expressions written out.)
+  NAZ_CFG_INLINE static constexpr int slot(int pi) { return pi; }
+  NAZ_CFG_INLINE static constexpr bool row_used(int r) { return r < P; }
+  NAZ_CFG_INLINE static constexpr int row_param(int r) { return r; }
   static constexpr int deg(int u) {
     if (C > 0) return ar_round_half_even(1.0 + (double)u * (double)(D - 1) / (double)(H - 1)) - 1;
     return ar_round_half_even(1.0 + (double)u * (double)(D - 2) / (double)(H - 1));
@@ -240,6 +365,28 @@ struct CfgAR {
   static constexpr int NW = WPE == 3 ? kARInvWaves : NW_FWD;
   static_assert(H <= 256 && D <= 32 && D >= 2 && NHID >= 1 && NHID <= 3, "unsupported fused autoregressive shape");
   static_assert(NOB <= 2 && NSTG <= 128, "output blocks / stages");
+};
+
+// order="linear" over the quadratic-spline CfgAR Q of the same shape: P = 4K - 1 = 31 parameters
+// per dim still fill NOB = 2 output blocks, so the inverse image's layout, stage plan and ring slot
+// are Q's (the sampler's image, CfgARF over this, has its own: NOG = 8 blocks per dim group).
+// Parameters 0 .. 3K - 2 keep their rows; λ_k (pi = 3K - 1 + k) goes to block 1, quarter 2 +
+// (k >> 2), register k & 3 (rls_select_inv_quad), which leaves row 3K - 1 an exact zero.  No
+// pass-0-constants form and no training instances.
+template <class Q>
+struct CfgARLin : Q {
+  static_assert(!Q::AFFINE && Q::K == 8, "the rational-linear spline on the K = 8 quarter layout");
+  static constexpr bool LINEAR = true;
+  static constexpr int P = 4 * Q::K - 1;
+  static constexpr int slot(int pi) { return pi < 3 * Q::K - 1 ? pi : pi + 1; }
+  static constexpr int row_param(int r) {
+    for (int pi = 0; pi < P; ++pi)
+      if (slot(pi) == r) return pi;
+    return -1;
+  }
+  static constexpr bool row_used(int r) { return row_param(r) >= 0; }
+  static_assert((P + 15) / 16 == Q::NOB && slot(P - 1) < 16 * Q::NOB && slot(3 * Q::K - 1) == 24,
+                "the parameters' rows lie in Q's output blocks, λ on quarters 2 | 3 of block 1");
 };
 
 // acc += sum over t < N of (A fragment t at LDS byte address ub + 2048 t, hi | lo 1 KB apart) x
@@ -345,10 +492,11 @@ static void made_ar_pack_layer(const float* flat, const int* perm, float* out) {
         for (int o = 0; o < CF::NOB; ++o)
           for (int t = 0; t < CF::kt(p); ++t)  // the output rows of dim d_p
             frag(st + (o * CF::kt(p) + t) * CF::OT, [&](int m, int kg, int j) -> float {
-              const int pi = 16 * o + m, v = r16_feat(t, kg, j);
-              return (pi < P && v < H) ? -2.f * Wl[CF::NHID][(pi * D + dp) * H + v] : 0.f;
+              const int r = 16 * o + m, pi = CF::row_param(r), v = r16_feat(t, kg, j);
+              return (CF::row_used(r) && v < H) ? -2.f * Wl[CF::NHID][(pi * D + dp) * H + v] : 0.f;
             });
-        for (int r = 0; r < 16 * CF::NOB; ++r) bias[r] = r < P ? bl[CF::NHID][r * D + dp] : 0.f;
+        for (int r = 0; r < 16 * CF::NOB; ++r)
+          bias[r] = CF::row_used(r) ? bl[CF::NHID][CF::row_param(r) * D + dp] : 0.f;
       }
     }
   }
@@ -479,7 +627,7 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::WPE) made_ar_r16_kernel(
         };
         const float4* bias4 = reinterpret_cast<const float4*>(cur + OFF_BIAS);
         bool done0 = false;
-        if constexpr (p == 0) {
+        if constexpr (p == 0 && !CF::LINEAR) {
           if (c0mode) {
             // one context vector (naz_ar_flow_pack with pass0): the degree-0 units and the first
             // dim's parameters are per-draw constants, written by the packer in place of this
@@ -575,7 +723,10 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::WPE) made_ar_r16_kernel(
             // one spline per row spread over its four quarters (rqs_select_inv_quad), not gathered
             // into and evaluated by every quarter
             float ld;
-            v[dp] = rqs_select_inv_quad<K>(o3[0], o3[CF::NOB > 1 ? 1 : 0], q, y, bound, rc, ld);
+            if constexpr (CF::LINEAR)
+              v[dp] = rls_select_inv_quad<K>(o3[0], o3[1], q, y, bound, rc, ld);
+            else
+              v[dp] = rqs_select_inv_quad<K>(o3[0], o3[CF::NOB > 1 ? 1 : 0], q, y, bound, rc, ld);
             ldsum -= ld;
           }
         }
@@ -626,7 +777,7 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::WPE) made_ar_r16_kernel(
 template <int D_, int C_, int H_, int NHID_>
 struct CfgARW {
   static constexpr int D = D_, C = C_, H = H_, K = 8, NHID = NHID_;
-  static constexpr bool AFFINE = true;
+  static constexpr bool AFFINE = true, LINEAR = false;
   static constexpr int P = 2, HP = (H + 31) / 32 * 32, HB = HP / 16, KSH = HP / 32;
   static constexpr int KC = (C + 31) / 32, KI = KC + 1, NOB = 1, OT = 2 * kChunk;
   static constexpr int deg(int u) {
@@ -649,7 +800,7 @@ struct CfgARF {
   // the forward spline's live set at D = 16 exceeds the 168 VGPRs of 12-wave workgroups (spilled
   // 352-468 B/lane): 8 waves (2 per SIMD) there
   static constexpr int NW = (G::AFFINE || D <= 8) ? G::NW_FWD : 8;
-  static constexpr bool AFFINE = G::AFFINE;
+  static constexpr bool AFFINE = G::AFFINE, LINEAR = G::LINEAR;
   static constexpr int NU = NHID * HB + NG;  // units: hidden (i, b) row-major, then one per dim group
   static constexpr int unit_blocks(int u) { return u < NHID * HB ? 1 : NOG; }
   // k-steps a hidden block b of layers 2.. reads: the units of degree <= the block's largest. The
@@ -907,7 +1058,7 @@ __global__ void made_ar_pack_kernel(const float* __restrict__ flat, int64_t sfla
   };
   unsigned word = 0;
   bool done = false;
-  if (c0 != nullptr) {  // pass-0 stages: only the constants, compact per stage (CfgAR::c0_off)
+  if (!CF::LINEAR && c0 != nullptr) {  // pass-0 stages: only the constants, compact per stage (CfgAR::c0_off)
     static_for<0, NHID + 1>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       constexpr int sb = CF::stage_id(0, i) * CF::STG, co = sb + CF::c0_off(i), cnt = CF::c0_cnt(i);
@@ -934,7 +1085,13 @@ __global__ void made_ar_pack_kernel(const float* __restrict__ flat, int64_t sfla
           const int u = 16 * (CF::blo(p) + r / 16) + r % 16;
           if (u < H) v = kSigScale * bl(i)[u];
         } else {
-          if (r < P) v = bl(NHID)[r * D + dp];
+          // (the row test written out where it is r < P: behind a call the optimizer folds it
+          // later, and the affine and quadratic instances' code would change)
+          if constexpr (CF::LINEAR) {
+            if (CF::row_used(r)) v = bl(NHID)[CF::row_param(r) * D + dp];
+          } else {
+            if (r < P) v = bl(NHID)[r * D + dp];
+          }
         }
         word = __builtin_bit_cast(unsigned, v);
         return;
@@ -964,8 +1121,8 @@ __global__ void made_ar_pack_kernel(const float* __restrict__ flat, int64_t sfla
           } else {
             constexpr int kts = CF::kt(p);
             const int o = fr / kts, t = fr % kts;
-            const int pi = 16 * o + m, vv = r16_feat(t, kg, j);
-            if (pi < P && vv < H) v = -2.f * wv(NHID, ((int64_t)pi * D + dp) * H + vv);
+            const int r = 16 * o + m, pi = CF::row_param(r), vv = r16_feat(t, kg, j);
+            if (CF::row_used(r) && vv < H) v = -2.f * wv(NHID, ((int64_t)pi * D + dp) * H + vv);
           }
           word |= ar_piece_dev(v, piece) << (16 * e);
         }
@@ -983,7 +1140,7 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::NW / 4) made_ar_fwd_kernel(
     const float* __restrict__ ctx, int64_t ldc, const float* __restrict__ low, const float* __restrict__ high,
     float* __restrict__ y, int64_t ldy, float* __restrict__ out_ld, int64_t B, float bound, int64_t spk = 0,
     int64_t sz = 0, int64_t sy = 0, int64_t sld = 0) {
-  constexpr int D = CF::D, K = CF::K, P = CF::P, NW = CF::NW, NHID = CF::NHID, HB = CF::HB, KSH = CF::KSH;
+  constexpr int D = CF::D, K = CF::K, NW = CF::NW, NHID = CF::NHID, HB = CF::HB, KSH = CF::KSH;
   {
     const int64_t dz = blockIdx.y;
     packed += dz * spk;
@@ -1121,13 +1278,20 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::NW / 4) made_ar_fwd_kernel(
         } else {
           float uw[K], uh[K], ud[K - 1];
 #pragma unroll
-          for (int pi = 0; pi < P; ++pi) {
+          for (int pi = 0; pi < 3 * K - 1; ++pi) {
             const float val = o3[pi >> 2][pi & 3];
             if (pi < K) uw[pi] = val;
             else if (pi < 2 * K) uh[pi - K] = val;
             else ud[pi - 2 * K] = val;
           }
-          yv = rqs_select<K, false>(uw, uh, ud, xv, bound, rc, ld);
+          if constexpr (CF::LINEAR) {
+            float ul[K];  // parameters 3K - 1 .. 4K - 2
+#pragma unroll
+            for (int k = 0; k < K; ++k) ul[k] = o3[(3 * K - 1 + k) >> 2][(3 * K - 1 + k) & 3];
+            yv = rls_select_fwd<K>(uw, uh, ud, ul, xv, bound, rc, ld);
+          } else {
+            yv = rqs_select<K, false>(uw, uh, ud, xv, bound, rc, ld);
+          }
         }
         ldsum += own ? ld : 0.f;  // summed over the quarters at the end
 #pragma unroll

@@ -28,7 +28,7 @@ class ArPass0:
     def __init__(self, desc, first: List[int], act: str, device):
         self.desc, self.act, self.dev = desc, act, device
         D, C, H, L, nh = desc.D, desc.C, desc.H, desc.L, desc.n_hidden
-        Q = 2 if desc.kind == ops.AR_KIND["maf"] else 3 * desc.K - 1
+        Q = ops.ar_params_per_dim(desc.kind, desc.K)
         deg = torch.as_tensor(ops.ar_flow_degrees(desc))
         self.e0 = e0 = int((deg == 0).sum())
         self.nb, self.nob, self.Q = (e0 + 15) // 16, (Q + 15) // 16, Q

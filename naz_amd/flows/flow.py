@@ -168,7 +168,7 @@ class _FusedAR:
         self.layers = layers
         self.kind = kind
         self.shape = (D, C, H, n_hidden, K)
-        self.P = 2 if kind == "maf" else 3 * K - 1
+        self.P = ops.ar_params_per_dim(ops.AR_KIND[kind], K)
         self.desc = ops.ar_flow_desc(kind, D, C, H, len(layers), n_hidden, K, act, bound)
         self.act = act
         self._sig = None
@@ -220,9 +220,10 @@ class _FusedAR:
         compiled shape of made_ar_bwd.h's spline instance (naz's own D=4 | C=2, H=[128,128], K=8;
         flows/nsa_grad.py: a saved-state forward plus one backward launch per layer).  Conditions:
         rows and context inside the f16 split's range, no gradient wanted for x or the context
-        (train's data).  Everything else keeps the autograd walk: other nsa shapes, order="linear",
-        active dropout, Permute layers and per-dim log-dets (their callers never reach the fused
-        plan).  NAZ_TRAIN_FUSED=0 keeps the walk everywhere."""
+        (train's data).  Everything else keeps the autograd walk: other nsa shapes, order="linear"
+        (kind "nsa_linear": fused log_prob and sample only), active dropout, Permute layers and
+        per-dim log-dets (their callers never reach the fused plan).  NAZ_TRAIN_FUSED=0 keeps the
+        walk everywhere."""
         if self.kind not in ("maf", "nsa") or _TRAIN_FUSED == "0" or x.dim() != 2 or x.requires_grad or \
                 (context is not None and context.requires_grad) or not self._train_kernels():
             return False
@@ -232,9 +233,10 @@ class _FusedAR:
         """maf: the fused backward kernel (made_ar_bwd.h) at its compiled shapes; elsewhere a fused
         inverse (naz_ar_flow_log_prob_train) + the GEMM-composed backward (flows/maf_grad_wide.py;
         NAZ_TRAIN_WIDE=0 keeps the autograd walk at the latter's shapes).  nsa: the spline instance
-        of the fused backward kernel, where compiled (naz_spline_ar_flow_bwd_packed_bytes > 0)."""
-        if self.kind == "nsa":
-            return self.inverse and ops.spline_ar_flow_bwd_supported(self.desc)
+        of the fused backward kernel, where compiled (naz_spline_ar_flow_bwd_packed_bytes > 0);
+        none for the linear order."""
+        if self.kind != "maf":
+            return self.kind == "nsa" and self.inverse and ops.spline_ar_flow_bwd_supported(self.desc)
         if ops.ar_flow_bwd_supported(self.desc):
             return True
         return _TRAIN_WIDE != "0" and self.inverse and ops.ar_flow_supported(self.desc) == 1
@@ -569,8 +571,9 @@ def _fused_plan(flow_type, flow_args, flow_kwargs, transforms):
     a = _maker_args(flow_type, flow_args, flow_kwargs)
     if a is None or "theta_dim" not in a:
         return None
-    if a.get("order", "quadratic") != "quadratic":
-        return None  # the fused whole-flow kernels evaluate the quadratic spline; linear runs per kernel
+    linear = a.get("order", "quadratic") != "quadratic"
+    if linear and (flow_type != "nsa" or a["order"] != "linear"):
+        return None  # order="linear" is fused for nsa only (log_prob and sample); nsc runs per kernel
     if flow_type in ("nsa", "maf") and _AR_FUSED != "0":
         D, C, hidden, L = a["theta_dim"], a["condition_dim"], a["hidden_dim"], a["num_layers"]
         K = a["count_bins"] if flow_type == "nsa" else 8
@@ -580,7 +583,8 @@ def _fused_plan(flow_type, flow_args, flow_kwargs, transforms):
             return None
         try:
             bound = transforms[0].bound if flow_type == "nsa" else 3.0
-            plan = _FusedAR(list(transforms), flow_type, D, C, hidden[0], len(hidden), K, act, bound)
+            kind = "nsa_linear" if linear else flow_type
+            plan = _FusedAR(list(transforms), kind, D, C, hidden[0], len(hidden), K, act, bound)
             if not ops.ar_flow_fwd_supported(plan.desc) or not plan.masks_ok():
                 return None
             plan.inverse = ops.ar_flow_supported(plan.desc)  # False: fused sampling only (wide MAFs)

@@ -743,14 +743,21 @@ def coupling_layer(d: CouplingDesc, packed: Tensor, layer: int, x: Tensor, conte
 
 
 # ----------------------------------------------------------------------------- §8b naz_{spline,affine}_ar_inv
-AR_KIND = {"nsa": 0, "maf": 1}  # NAZ_AR_SPLINE, NAZ_AR_AFFINE
+AR_KIND = {"nsa": 0, "maf": 1, "nsa_linear": 2}  # NAZ_AR_SPLINE, NAZ_AR_AFFINE, NAZ_AR_SPLINE_LINEAR
+
+
+def ar_params_per_dim(kind: int, K: int) -> int:
+    """ARN outputs per dim of a naz_ar_desc kind: (mean, log_scale), or the spline's 3K - 1
+    (quadratic) / 4K - 1 (linear: one λ per bin more) parameters."""
+    return 2 if kind == AR_KIND["maf"] else (4 * K - 1 if kind == AR_KIND["nsa_linear"] else 3 * K - 1)
 AR_CLIP_ZERO_GRAD = 1  # naz_ar_desc.flags: NAZ_AR_CLIP_ZERO_GRAD
 AFFINE_CLIP_ZERO_GRAD = 2  # naz_affine_ar_bwd / naz_maf_dim_vjp mode bit: NAZ_AFFINE_CLIP_ZERO_GRAD
 
 
 def ar_flow_desc(kind: str, D: int, C: int, H: int, L: int, n_hidden: int = 2, K: int = 8, act: str = "tanh",
                  bound: float = 3.0) -> ArDesc:
-    """naz_ar_desc of an L-layer nsa / maf flow with n_hidden tanh hidden layers of width H."""
+    """naz_ar_desc of an L-layer nsa / maf flow with n_hidden tanh hidden layers of width H
+    (kind: "nsa", "maf", or "nsa_linear" for an nsa flow of order="linear")."""
     d = ArDesc()
     d.D, d.C, d.H, d.K, d.L = D, C, H, K, L
     d.act, d.bound = ACT.get(act, -1), float(bound)
@@ -791,7 +798,7 @@ def ar_executed_flop_per_row(d: ArDesc, pass0_const: bool = False) -> dict:
     pass0_const: the images carry the first degree pass as per-draw constants (no MFMAs in pass 0).
     """
     D, C, H, NH, L = d.D, d.C, d.H, d.n_hidden, d.L
-    P = 2 if d.kind == AR_KIND["maf"] else 3 * d.K - 1
+    P = ar_params_per_dim(d.kind, d.K)
     HP = (H + 31) // 32 * 32
     HB, KSH, KI, NOB = HP // 16, HP // 32, (C + 31) // 32 + 1, (P + 15) // 16
     blk = 16 * 32 * 2  # one 16-unit block over one 32-deep k-step, per row
