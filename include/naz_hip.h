@@ -490,6 +490,26 @@ int naz_ar_flow_sample_batched(const naz_ar_desc* d, const void* packed, int64_t
                                int64_t sz, const float* ctx, int64_t ldc, float* y, int64_t ldy, int64_t sy,
                                float* out_ld, int64_t sld, int64_t B, int64_t P, void* stream);
 
+/* §8f rank 2: MC-dropout sampling (naz MCDPNormalizingFlow.sample_uncertain, mcdpflow.py:39-56; any
+ * sample of a dropout_p flow in train mode) in one launch: naz_ar_flow_sample with nn.Dropout(p) after
+ * every hidden activation, batched over P dropout draws of ONE flow.  packed_fwd is the forward image
+ * of naz_ar_flow_pack_fwd_host / naz_ar_flow_pack_fwd (one image, shared by every draw).  Draw i maps
+ * z + i sz -> y + i sy (B rows each, row strides ldz / ldy), out_ld + i sld (nullable) = Σ forward
+ * log-dets; ctx is shared by every draw (ldc = 0: one context vector); low / high: inverse bounding
+ * of y.  seeds: DEVICE array [P][L][n_hidden] of 64-bit seeds, one per (draw, layer, hidden layer);
+ * the masks are exactly the ones naz_dropout(p, seed) applies to the [B, H] activation of that
+ * hidden layer, with row index = the row's index in the call + row_offset (so a batch may be split
+ * over calls).  0 <= p < 1; p whose scale 1 / (1 - p) exceeds 65536 is refused with an error (the
+ * scaled activation would leave the kernel's f16 pieces).  P <= 65535 per call; B == 0 or P == 0 is
+ * a no-op.  Nothing allocates; the launch is graph-capturable (no seed in the kernel arguments).
+ * naz_ar_flow_sample_dropout_supported: 1 where an instance exists (maf D=2|C=2 and D=4|C=2 at
+ * H=[150]x3; quadratic nsa D=4|C=2, H=[128,128], K=8), else 0. */
+int naz_ar_flow_sample_dropout_supported(const naz_ar_desc* d);
+int naz_ar_flow_sample_dropout(const naz_ar_desc* d, const void* packed_fwd, const float* z, int64_t ldz, int64_t sz,
+                               const float* ctx, int64_t ldc, const float* low, const float* high, float* y,
+                               int64_t ldy, int64_t sy, float* out_ld, int64_t sld, int64_t B, int64_t P, float p,
+                               const uint64_t* seeds, int64_t row_offset, void* stream);
+
 /* §8f rank 1: the log-density batched over P weight draws (naz's Bayesian MAF lp over the training
  * set per posterior draw, bflow_jax_maf.py:196-225 log_prob vmapped over draws: the NUTS potential
  * of calibrate.py).  naz_ar_flow_pack packs the inverse images of P draws ON THE DEVICE: flat rows

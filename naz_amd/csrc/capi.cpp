@@ -661,6 +661,30 @@ int naz_ar_flow_sample_batched(const naz_ar_desc* d, const void* packed, int64_t
   return ar_flow_sample_batched(d, body, spk, z, ldz, sz, ctx, ldc, y, ldy, sy, out_ld, sld, B, P, as_stream(stream));
 }
 
+int naz_ar_flow_sample_dropout_supported(const naz_ar_desc* d) { return ar_flow_sample_dropout_supported(d); }
+int naz_ar_flow_sample_dropout(const naz_ar_desc* d, const void* packed_fwd, const float* z, int64_t ldz, int64_t sz,
+                               const float* ctx, int64_t ldc, const float* low, const float* high, float* y,
+                               int64_t ldy, int64_t sy, float* out_ld, int64_t sld, int64_t B, int64_t P, float p,
+                               const uint64_t* seeds, int64_t row_offset, void* stream) {
+  const char* const fn = "naz_ar_flow_sample_dropout";
+  if (d == nullptr) return set_error("%s: null descriptor", fn);
+  if (B < 0 || P < 0) return set_error("%s: negative size", fn);
+  if (P > 65535) return set_error("%s: at most 65535 draws per call", fn);
+  if (!(p >= 0.f && p < 1.f)) return set_error("%s: p must be in [0, 1)", fn);
+  if ((low == nullptr) != (high == nullptr)) return set_error("%s: low/high must both be set", fn);
+  if (!ar_flow_sample_dropout_supported(d))
+    return set_error("%s: no dropout sampler for kind=%d D=%d C=%d H=%d x %d K=%d act=%d", fn, d->kind, d->D, d->C,
+                     d->H, d->n_hidden, d->K, d->act);
+  if (B == 0 || P == 0) return 0;
+  if (packed_fwd == nullptr || z == nullptr || y == nullptr || seeds == nullptr)
+    return set_error("%s: null pointer", fn);
+  if (d->C > 0 && ctx == nullptr) return set_error("%s: conditional flow needs ctx", fn);
+  if (d->L < 1) return set_error("%s: a flow of at least one layer", fn);
+  NAZ_IMG(fn, spec_ar(d, IMG_AR_FWD), packed_fwd, 1, 0, 0, body);
+  return ar_flow_sample_dropout(d, body, z, ldz, sz, ctx, ldc, low, high, y, ldy, sy, out_ld, sld, B, P, p, seeds,
+                                row_offset, as_stream(stream));
+}
+
 int64_t naz_ar_flow_pass0_floats(const naz_ar_desc* d) { return ar_flow_pass0_floats(d); }
 int naz_ar_flow_pack(const naz_ar_desc* d, const float* flat, int64_t sflat, const int* perm, void* packed, int64_t spk,
                      int64_t P, const float* pass0, int64_t sp0, const float* mask, void* stream) {

@@ -122,6 +122,12 @@ int ar_flow_pack_fwd(const naz_ar_desc* d, const float* flat, int64_t sflat, voi
 int ar_flow_sample_batched(const naz_ar_desc* d, const void* packed, int64_t spk, const float* z, int64_t ldz,
                            int64_t sz, const float* ctx, int64_t ldc, float* y, int64_t ldy, int64_t sy, float* out_ld,
                            int64_t sld, int64_t B, int64_t P, hipStream_t s);
+// made_ar_dropout.hip: the fused sampler with MC dropout after every hidden activation
+int ar_flow_sample_dropout_supported(const naz_ar_desc* d);
+int ar_flow_sample_dropout(const naz_ar_desc* d, const void* packed, const float* z, int64_t ldz, int64_t sz,
+                           const float* ctx, int64_t ldc, const float* low, const float* high, float* y, int64_t ldy,
+                           int64_t sy, float* out_ld, int64_t sld, int64_t B, int64_t P, float p,
+                           const uint64_t* seeds, int64_t row_offset, hipStream_t s);
 int64_t ar_flow_pass0_floats(const naz_ar_desc* d);
 int ar_flow_pack(const naz_ar_desc* d, const float* flat, int64_t sflat, const int* perm, void* packed, int64_t spk,
                  int64_t P, const float* pass0, int64_t sp0, const float* mask, hipStream_t s);

@@ -97,6 +97,10 @@ class TransformedDistribution:
                 getattr(self._fused, "sample_ready", lambda *a: True)(z, self._context):
             y, _ = self._fused.sample(z, self._context, bounds=bounds)
             return y
+        if self._dropout_fused(z):
+            # MC dropout active at a compiled shape: still one launch (naz_ar_flow_sample_dropout)
+            y, _ = self._fused.sample_dropout(z, self._context, bounds=bounds)
+            return y
         ld = torch.zeros(z.shape[0], device=z.device, dtype=torch.float32)
         y = z
         for t in self.transforms:
@@ -104,6 +108,27 @@ class TransformedDistribution:
         if bounds is not None:
             y = ops.bounding_inv(y, bounds["low"], bounds["high"])
         return y
+
+    def _dropout_fused(self, z2d: torch.Tensor) -> bool:
+        """The fused plan samples with its conditioners' MC dropout active (one launch), under the
+        fused sampler's own conditions (sample_ready)."""
+        f = self._fused
+        return f is not None and getattr(f, "can_sample", True) and \
+            getattr(f, "dropout_sample_usable", lambda: False)() and f.sample_ready(z2d, self._context)
+
+    def sample_dropout_draws(self, draws: int, sample_shape=torch.Size(), bounds=None) -> Optional[torch.Tensor]:
+        """``draws`` sample sets of ``sample_shape``, each from fresh base draws and fresh dropout
+        masks, in ONE launch: [draws, *sample_shape, D]; None where the fused dropout sampler does
+        not apply (the caller then loops over sample())."""
+        shape = torch.Size(sample_shape)
+        loc = self.base_dist.loc
+        D = loc.shape[-1]
+        if not self._dropout_fused(loc.new_empty((0, D))):  # (decided before any random number is drawn)
+            return None
+        with torch.no_grad():
+            z = torch.randn((int(draws), shape.numel(), D), device=loc.device, dtype=torch.float32)
+            y, _ = self._fused.sample_dropout(z, self._context, bounds=bounds)
+        return y.reshape((int(draws),) + shape + (D,))
 
     def rsample(self, sample_shape=torch.Size(), bounds=None) -> torch.Tensor:
         shape = torch.Size(sample_shape)

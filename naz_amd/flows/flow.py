@@ -321,6 +321,47 @@ class _FusedAR:
             low, high = bounds["low"].contiguous(), bounds["high"].contiguous()
         return ops.ar_flow_sample(self.desc, self.packed_fwd(), z, context, low, high, with_logdet=with_logdet)
 
+    def dropout_p(self) -> Optional[float]:
+        """The conditioners' common dropout probability while every one's MC dropout is active
+        (train mode, dropout_p > 0); None otherwise."""
+        nets = self._nets()
+        if not nets or not all(n.dropout_active() for n in nets):
+            return None
+        p = float(nets[0].dropout_p)
+        return p if all(float(n.dropout_p) == p for n in nets) else None
+
+    def dropout_sample_usable(self) -> bool:
+        """sample() of the flow with MC dropout active runs as one naz_ar_flow_sample_dropout launch:
+        pyro's masks, every conditioner's dropout active with one common p inside the kernel's
+        range (1 / (1 - p) <= ops.AR_DROPOUT_MAX_SCALE), and a dropout instance of the sampler at
+        this shape.  NAZ_AR_DROPOUT_FUSED=0 keeps the per-layer path (read at every call)."""
+        if os.environ.get("NAZ_AR_DROPOUT_FUSED", "1") == "0" or not self.masks_ok():
+            return False
+        p = self.dropout_p()
+        if p is None or not 0.0 <= p < 1.0 or 1.0 / (1.0 - p) > ops.AR_DROPOUT_MAX_SCALE:
+            return False
+        if getattr(self, "_dropform", None) is None:
+            self._dropform = ops.ar_flow_sample_dropout_supported(self.desc)
+        return self._dropform
+
+    def dropout_seeds(self, draws: int, device) -> torch.Tensor:
+        """[draws, L, n_hidden] int64 seeds on ``device``, drawn as the per-layer path draws them:
+        per draw, each layer's conditioner in order (torch's CPU generator, _DropoutMixin._drop_args),
+        so torch.manual_seed makes a run reproducible."""
+        seeds = [[n._drop_args()[1] for n in self._nets()] for _ in range(int(draws))]
+        return torch.tensor(seeds, dtype=torch.int64).reshape(int(draws), len(self.layers), -1).to(device)
+
+    def sample_dropout(self, z, context=None, bounds=None, with_logdet=False, seeds=None, row_offset=0):
+        """sample() with MC dropout (dropout_sample_usable): z [B, D], or [P, B, D] for P dropout draws
+        in one launch; fresh seeds unless given ([L, n_hidden] / [P, L, n_hidden])."""
+        low = high = None
+        if bounds is not None:
+            low, high = bounds["low"].contiguous(), bounds["high"].contiguous()
+        if seeds is None:
+            seeds = self.dropout_seeds(1 if z.dim() == 2 else z.shape[0], z.device)
+        return ops.ar_flow_sample_dropout(self.desc, self.packed_fwd(), z, context, low, high, self.dropout_p(), seeds,
+                                          row_offset=row_offset, with_logdet=with_logdet)
+
     def _pass0_operands(self):
         """(unmasked flat rows [1, L per], mask vector, permutations, ArPass0) on the device, for
         the one-context-vector path; re-read when a parameter, mask or permutation changes."""

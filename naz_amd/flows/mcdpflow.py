@@ -26,14 +26,32 @@ class MCDPNormalizingFlow(NormalizingFlow):
         self.flow_maker = args[0]
         assert kwargs.get("dropout_p") not in [None, 0.0], "MCDPNormalizingFlow needs dropout_p > 0"
 
+    # rows (iterations x sample rows) per fused launch: z and y of one chunk are 2 x ROW_BUDGET x D
+    # floats on the device (64 MB each at D = 4)
+    ROW_BUDGET = 1 << 22
+
     def sample_uncertain(self, niter, *args, condition=None, **kwargs):
-        """mcdpflow.py:39-56: ``niter`` stochastic forward passes in train mode."""
+        """mcdpflow.py:39-56: ``niter`` stochastic forward passes in train mode.
+
+        Where the fused dropout sampler applies (a maf / nsa flow at a compiled shape,
+        naz_ar_flow_sample_dropout), the base draws and dropout seeds of a chunk of iterations are
+        drawn at once and the chunk is ONE launch, then copied to the host; a chunk holds as many
+        iterations as keep iterations x rows at or below ROW_BUDGET = 2^22 rows (at least one).
+        Otherwise one sample() per iteration on the per-layer kernels."""
         self.train()
         pdf = self._pdf(condition)
         bounds = self._bounds_dev(self._base_loc)
         shape = args[0] if args else kwargs.get("sample_shape", ())
+        niter = int(niter)
+        rows = max(int(torch.Size(shape).numel()), 1)
+        chunk = max(1, self.ROW_BUDGET // rows)
         out = []
         with torch.no_grad():
-            for _ in range(int(niter)):
-                out.append(pdf.sample(shape, bounds=bounds).cpu().numpy())
+            while len(out) < niter:
+                n = min(chunk, niter - len(out))
+                ys = pdf.sample_dropout_draws(n, shape, bounds=bounds) if hasattr(pdf, "sample_dropout_draws") else None
+                if ys is None:
+                    out.append(pdf.sample(shape, bounds=bounds).cpu().numpy())
+                else:
+                    out.extend(ys.cpu().numpy())
         return np.array(out)

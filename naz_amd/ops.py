@@ -906,6 +906,44 @@ def ar_flow_sample_batched(d: ArDesc, packed: Tensor, z: Tensor, context: Option
     return y, ld
 
 
+def ar_flow_sample_dropout_supported(d: ArDesc) -> bool:
+    """The fused sampler has an MC-dropout instance for this shape (naz_ar_flow_sample_dropout)."""
+    return int(lib().naz_ar_flow_sample_dropout_supported(d)) == 1
+
+
+AR_DROPOUT_MAX_SCALE = 65536.0  # naz_ar_flow_sample_dropout refuses 1 / (1 - p) beyond it (f16 pieces)
+
+
+def ar_flow_sample_dropout(d: ArDesc, packed_fwd: Tensor, z: Tensor, context: Optional[Tensor], low: Optional[Tensor],
+                           high: Optional[Tensor], p: float, seeds: Tensor, row_offset: int = 0,
+                           with_logdet: bool = False) -> Tuple[Tensor, Optional[Tensor]]:
+    """``ar_flow_sample`` with MC dropout after every hidden activation, one launch
+    (naz_ar_flow_sample_dropout).  z [B, D] (one draw) or [P, B, D] (P dropout draws of the same
+    flow and context); seeds: int64 device tensor [L, n_hidden] or [P, L, n_hidden], one per (draw,
+    layer, hidden layer) — the masks are ``ops.dropout``'s for the same seed on the [B, H]
+    activation, rows counted from ``row_offset``.  Returns (y like z, Σ forward log-dets [B] /
+    [P, B] or None)."""
+    dev = _dev(packed_fwd, z, context, low, high)
+    single = z.dim() == 2
+    if z.dim() not in (2, 3) or z.dtype != torch.float32:
+        raise ValueError("ar_flow_sample_dropout: z must be a float32 [B, D] or [P, B, D] tensor")
+    z3 = (z[None] if single else z).contiguous()
+    P, B, D = z3.shape
+    if seeds.dtype != torch.int64 or seeds.device != dev or seeds.numel() != P * d.L * d.n_hidden:
+        raise ValueError("ar_flow_sample_dropout: seeds must be an int64 tensor of P * L * n_hidden elements on "
+                         "z's device")
+    seeds = seeds.contiguous()
+    context, ldc = _ctx_arg(context, B)
+    y = torch.empty_like(z3)
+    ld = torch.empty((P, B), device=dev, dtype=torch.float32) if with_logdet else None
+    check(lib().naz_ar_flow_sample_dropout(d, _p(packed_fwd), _p(z3), D, B * D, _p(context), ldc, _p(low), _p(high),
+                                           _p(y), D, B * D, _p(ld), B, B, P, float(p), _p(seeds), int(row_offset),
+                                           _stream(dev)), "ar_flow_sample_dropout")
+    if single:
+        return y[0], (None if ld is None else ld[0])
+    return y, ld
+
+
 _AR_PERMS: dict = {}
 
 
