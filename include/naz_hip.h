@@ -502,8 +502,8 @@ int naz_ar_flow_sample_batched(const naz_ar_desc* d, const void* packed, int64_t
  * over calls).  0 <= p < 1; p whose scale 1 / (1 - p) exceeds 65536 is refused with an error (the
  * scaled activation would leave the kernel's f16 pieces).  P <= 65535 per call; B == 0 or P == 0 is
  * a no-op.  Nothing allocates; the launch is graph-capturable (no seed in the kernel arguments).
- * naz_ar_flow_sample_dropout_supported: 1 where an instance exists (maf D=2|C=2 and D=4|C=2 at
- * H=[150]x3; quadratic nsa D=4|C=2, H=[128,128], K=8), else 0. */
+ * naz_ar_flow_sample_dropout_supported: 1 where an instance exists (maf D=2|C=2, D=2|C=0 and
+ * D=4|C=2 at H=[150]x3; quadratic nsa D=4|C=2, H=[128,128], K=8), else 0. */
 int naz_ar_flow_sample_dropout_supported(const naz_ar_desc* d);
 int naz_ar_flow_sample_dropout(const naz_ar_desc* d, const void* packed_fwd, const float* z, int64_t ldz, int64_t sz,
                                const float* ctx, int64_t ldc, const float* low, const float* high, float* y,
@@ -538,7 +538,8 @@ int naz_ar_flow_log_prob_batched(const naz_ar_desc* d, const void* packed, int64
  * (naz/flows/bflow_jax_maf.py:231-235; examples/papers/2506.05657/hmc_maf_exact.py:118-133) and
  * loss.backward() of a maf NLL (naz/trainers/train_flows.py:194-213).  Affine autoregressive flows
  * at the compiled shapes (naz_ar_flow_bwd_packed_bytes < 0 otherwise; the paper shape
- * D=2 | C=2, H=[150]x3 and the 4-parameter Bayesian D=4 | C=2, H=[150]x3).
+ * D=2 | C=2, H=[150]x3, its unconditional form D=2 | C=0 (ctx = NULL) and the 4-parameter Bayesian
+ * D=4 | C=2, H=[150]x3).
  *   naz_ar_flow_log_prob_train: naz_ar_flow_log_prob (one draw, no bounding) that also writes
  *     states [L][B][D]: states[l] = s_l, layer l's output (layer l maps s_{l+1} -> s_l; s_0 = z).
  *     Every affine flow whose inverse is fused (naz_ar_flow_supported == 1): at the shapes without

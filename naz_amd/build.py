@@ -23,11 +23,11 @@ ARCH = os.environ.get("NAZ_OFFLOAD_ARCH", "gfx950")
 # ops it forms (v_pk_add/mul/fma_f32) issue slower than scalar ones beside MFMAs, and the
 # packing moves add register pressure (spills in coupling_x6_kernel with it on).
 SOURCE_FLAGS = {s: ["-fno-slp-vectorize"]
-                for s in ("coupling.hip", "made_ar.hip", "made_ar_linear.hip", "made_ar_dropout.hip", "made_ar_bwd.hip",
-                          "cnf.hip", "made.hip")}
+                for s in ("coupling.hip", "made_ar.hip", "made_ar_linear.hip", "made_ar_uncond.hip", "made_ar_dropout.hip",
+                          "made_ar_bwd.hip", "cnf.hip", "made.hip")}
 SOURCES = ["rqs.hip", "rls.hip", "dense.hip", "gemm.hip", "gemm_rows.hip", "elementwise.hip", "made.hip",
-           "coupling.hip", "made_ar.hip", "made_ar_linear.hip", "made_ar_dropout.hip", "made_ar_bwd.hip", "cnf.hip",
-           "capi.cpp"]
+           "coupling.hip", "made_ar.hip", "made_ar_linear.hip", "made_ar_uncond.hip", "made_ar_dropout.hip", "made_ar_bwd.hip",
+           "cnf.hip", "capi.cpp"]
 
 
 def hipcc() -> str:

@@ -2,6 +2,7 @@
 // over made_ar_r16.h (log_prob and sample) and made_ar_wide.h (the wide production MAFs).
 #include "made_ar_linear.h"
 #include "made_ar_r16.h"
+#include "made_ar_uncond.h"
 #include "made_ar_wide.h"
 #include "naz_internal.h"
 
@@ -13,6 +14,8 @@ namespace naz {
 // the linear-order instances' kernels are compiled in made_ar_linear.hip
 NAZ_AR_LIN_KERNELS(extern, ArLin4x2)
 NAZ_AR_LIN_KERNELS(extern, ArLin8x0)
+// ... and the unconditional paper maf's in made_ar_uncond.hip
+NAZ_AR_LIN_KERNELS(extern, ArMaf2x0)
 
 // ---- forward (sample) direction, shared by AROps and AROpsW: made_ar_fwd_kernel over CfgARF<G>'s
 // per-layer image
@@ -78,6 +81,8 @@ struct AROps : ARFwdOps<CF> {
                       float* states = nullptr, void* = nullptr, int64_t = 0) {
     static_assert(2 * CF::STG * 4 <= 160 * 1024, "two weight stages exceed the LDS");
     if (c0mode && CF::LINEAR) return set_error("naz_ar_flow: the linear-order spline has no pass-0 constants form");
+    if (c0mode && CF::CUT) return set_error("naz_ar_flow: D=%d C=%d H=%d x %d: no pass-0 constants form", CF::D, CF::C,
+                                            CF::H, CF::NHID);
     if (B == 0 || L == 0 || P == 0) return 0;
     if (P > 65535) return set_error("naz_ar_flow_log_prob_batched: at most 65535 draws per call");
     const int64_t rows = 16 * CF::NW, grid = (B + rows - 1) / rows;
@@ -87,12 +92,15 @@ struct AROps : ARFwdOps<CF> {
     return check_launch("made_ar_r16_kernel");
   }
   static int64_t workspace_bytes(int64_t, int64_t) { return 0; }  // every intermediate stays on chip
-  static int64_t pass0_floats() { return CF::LINEAR ? -1 : CF::C0; }
+  // (a layout with cut sub-layers has none either: the one such shape has no context to fold)
+  static int64_t pass0_floats() { return CF::LINEAR || CF::CUT ? -1 : CF::C0; }
   static int pack_device(const float* flat, int64_t sflat, const int* perm, float* packed, int64_t spk, int L,
                          int64_t P, hipStream_t s, const float* c0 = nullptr, int64_t sc0 = 0,
                          const float* mask = nullptr) {
     if (c0 != nullptr && CF::LINEAR)
       return set_error("naz_ar_flow_pack: the linear-order spline has no pass-0 constants form");
+    if (c0 != nullptr && CF::CUT)
+      return set_error("naz_ar_flow_pack: D=%d C=%d H=%d x %d: no pass-0 constants form", CF::D, CF::C, CF::H, CF::NHID);
     if (L == 0 || P == 0) return 0;
     if (P > 65535 || L > 65535) return set_error("naz_ar_flow_pack: at most 65535 draws / layers per call");
     const dim3 grid((unsigned)((CF::LAYER + 255) / 256), (unsigned)L, (unsigned)P);
@@ -195,6 +203,8 @@ static int ar_dispatch(const naz_ar_desc* d, F&& f) {
     // K is unused (the instances carry 8); the maf paper shape (train_mle_all_data.py:62-70) and
     // SURVEY §8d's config-3 AR variant
     if (d->D == 2 && d->C == 2 && d->H == 150 && d->n_hidden == 3) return f(AROps<CfgAR<2, 2, 150, 8, 3, true>>{});
+    // the unconditional paper maf (train_mle_unsupervised.py)
+    if (d->D == 2 && d->C == 0 && d->H == 150 && d->n_hidden == 3) return f(AROps<ArMaf2x0>{});
     // the 4-parameter Bayesian MAF (calibrate_4p.py:75,90-96; hmc_maf_exact.py:101-133)
     if (d->D == 4 && d->C == 2 && d->H == 150 && d->n_hidden == 3) return f(AROps<CfgAR<4, 2, 150, 8, 3, true>>{});
     if (d->D == 16 && d->C == 32 && d->H == 128 && d->n_hidden == 2) return f(AROps<CfgAR<16, 32, 128, 8, 2, true>>{});

@@ -2,12 +2,16 @@
 // maf NLL step, ar_flow_bwd_* and ar_flow_pack_bwd; and of its spline instance, the nsa NLL step,
 // spline_ar_flow_bwd_* and spline_ar_flow_pack_bwd.
 #include "made_ar_bwd.h"
+#include "made_ar_uncond.h"
 #include "naz_internal.h"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace naz {
+
+// the unconditional paper maf's kernels are compiled in made_ar_uncond.hip
+NAZ_AR_BWD_KERNELS(extern, ArMaf2x0)
 
 template <class CF>
 struct ARBwdOps {
@@ -49,6 +53,8 @@ static int ar_bwd_dispatch(const naz_ar_desc* d, F&& f) {
   if (d->D == 2 && d->C == 2 && d->H == 150 && d->n_hidden == 3) return f(ARBwdOps<CfgAR<2, 2, 150, 8, 3, true>>{});
   // the 4-parameter Bayesian MAF's NUTS potential (calibrate_4p.py:75,90-96; hmc_maf_exact.py:101-133)
   if (d->D == 4 && d->C == 2 && d->H == 150 && d->n_hidden == 3) return f(ARBwdOps<CfgAR<4, 2, 150, 8, 3, true>>{});
+  // the unconditional paper maf's NLL step (train_mle_unsupervised.py)
+  if (d->D == 2 && d->C == 0 && d->H == 150 && d->n_hidden == 3) return f(ARBwdOps<ArMaf2x0>{});
   return -2;
 }
 

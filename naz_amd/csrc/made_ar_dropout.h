@@ -141,6 +141,10 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::NW / 4) made_ar_fwd_drop_kern
         }
         ++g;
       }
+      // the unconditional maf (one degree class: every hidden block of layers 2.. reads all KSH
+      // k-steps): scheduled freely across units the D=2 | C=0 instance needs one register more than
+      // the 256 of its launch bounds (8 B/lane of scratch); one unit at a time it fits with none
+      if constexpr (CF::AFFINE && CF::C == 0) __builtin_amdgcn_sched_barrier(0);
       const u32x4* c4 = reinterpret_cast<const u32x4*>(cur);
       auto afrag = [&](int idx) {
         const int base = (OFF >> 2) + idx * 128 + lane;
@@ -222,6 +226,7 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::NW / 4) made_ar_fwd_drop_kern
 // the instances: compiled in made_ar_dropout.hip, launched from there
 using ArDropMaf2x2 = CfgARF<CfgAR<2, 2, 150, 8, 3, true>>;  // the paper maf
 using ArDropMaf4x2 = CfgARF<CfgAR<4, 2, 150, 8, 3, true>>;  // the 4-parameter maf
+using ArDropMaf2x0 = CfgARF<CfgAR<2, 0, 150, 8, 3, true>>;  // the unconditional paper maf
 using ArDropNsa4x2 = CfgARF<CfgAR<4, 2, 128, 8>>;           // naz's own nsa shape (quadratic)
 
 }  // namespace naz

@@ -30,6 +30,7 @@ static int drop_dispatch(const naz_ar_desc* d, F&& f) {
     if (d->D == 2) return f(ArDropMaf2x2{});
     if (d->D == 4) return f(ArDropMaf4x2{});
   }
+  if (d->kind == NAZ_AR_AFFINE && d->D == 2 && d->C == 0 && d->H == 150 && d->n_hidden == 3) return f(ArDropMaf2x0{});
   return -2;
 }
 

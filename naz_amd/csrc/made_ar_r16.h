@@ -25,7 +25,8 @@
 //   pyro's D full passes; the conditioner work is one triangular network per layer instead of D.
 // Weights stream through the coupling kernels' two-slot LDS-DMA ring: the per-pass sub-layers
 // (hidden layer 1, 2, ..., output) are grouped greedily into stages of at most kARCap floats
-// (nsa at H = 128: one stage per pass).  x stays in registers in natural dim order (the uniform
+// (nsa at H = 128: one stage per pass; a sub-layer larger than that — the unconditional D = 2 maf's,
+// whose units all share one degree — is cut at block boundaries first).  x stays in registers in natural dim order (the uniform
 // dim index d_p addresses it through M0-relative moves).
 #pragma once
 #include "coupling_r16.h"
@@ -274,13 +275,31 @@ struct CfgAR {
   }
   static constexpr int pad(int n) { return (n + 255) / 256 * 256; }
   // the per-layer plan, computed once per instantiation (a table: the nested constexpr calls of a
-  // direct formulation exceed the compiler's constant-evaluation step limit)
+  // direct formulation exceed the compiler's constant-evaluation step limit).
+  // A hidden sub-layer larger than a ring slot (every unit of one degree: the unconditional D = 2
+  // maf, whose 150 units per hidden layer all have degree 1) is cut at 16-unit block boundaries
+  // into the fewest near-equal parts that fit; a part is a sub-layer image of its own blocks
+  // ([fragments (block, k-step)] [bias: 16 per block]) and is grouped into stages like one.  Where
+  // nothing exceeds kARCap every sub-layer is its one part 0 and the plan is the uncut one.  (The
+  // parts have a table of their own, read in constant expressions only: Layout, which the packers
+  // index at run time, keeps its size, and so do the device images' constant data.)
+  static constexpr int kMaxParts = 4;
   struct Layout {
     int E[32];         // E[p] = number of hidden units of degree <= p (a prefix: degrees are non-decreasing)
-    int sid[32][4];    // stage holding sub-layer i of pass p
+    int sid[32][4];    // stage holding sub-layer i of pass p (its part 0)
     int off[32][4];    // its offset in the stage (floats)
     int sfl[128];      // floats of stage s (padded)
     int nstg, stg;
+  };
+  struct Parts {
+    int np[32][4];              // parts of sub-layer i of pass p (1: not cut)
+    int sid[32][4][kMaxParts];  // stage holding part j
+    int off[32][4][kMaxParts];  // its offset in the stage (floats)
+    bool cut;                   // some sub-layer has more than one part
+  };
+  struct Plan {
+    Layout ly;
+    Parts pt;
   };
   static constexpr int E_of(const Layout& y, int p) { return p < 0 ? 0 : y.E[p]; }
   static constexpr int blo_of(const Layout& y, int p) { return E_of(y, p - 1) >> 4; }
@@ -297,40 +316,92 @@ struct CfgAR {
   static constexpr int sub_floats_of(const Layout& y, int p, int i) {
     return frags_of(y, p, i) * OT + 16 * (i < NHID ? nb_of(y, p) : NOB);
   }
-  static constexpr Layout make_layout() {
-    Layout y{};
+  // part j of n of a hidden sub-layer: the pass's blocks [pblo, pblo + pnb) (relative to blo(p))
+  static constexpr int pblo_of(const Layout& y, int p, int n, int j) { return j * nb_of(y, p) / n; }
+  static constexpr int pnb_of(const Layout& y, int p, int n, int j) {
+    return pblo_of(y, p, n, j + 1) - pblo_of(y, p, n, j);
+  }
+  static constexpr int part_floats_of(const Layout& y, int p, int i, int n, int j) {
+    if (n == 1) return sub_floats_of(y, p, i);
+    return pnb_of(y, p, n, j) * ((i == 0 ? KI : kt_of(y, p)) * OT + 16);
+  }
+  static constexpr Plan make_plan() {
+    Plan pl{};
+    Layout& y = pl.ly;
+    Parts& t = pl.pt;
     int cnt[32] = {};
     for (int u = 0; u < H; ++u) ++cnt[deg(u) < 0 ? 0 : deg(u)];
     for (int p = 0, run = 0; p < D; ++p) y.E[p] = run += cnt[p];
-    // greedy grouping of each pass's sub-layers into stages of <= kARCap floats
+    // greedy grouping of each pass's sub-layers (their parts) into stages of <= kARCap floats
     int s = -1;
     for (int p = 0; p < D; ++p) {
       int run = 0;
       for (int i = 0; i <= NHID; ++i) {
-        const int sz = sub_floats_of(y, p, i);
-        if (i == 0 || run + sz > kARCap) {
-          ++s;
-          run = 0;
+        int n = 1;
+        if (i < NHID)
+          while (n < kMaxParts && part_floats_of(y, p, i, n, n - 1) > kARCap) ++n;  // (the last part is a largest)
+        t.np[p][i] = n;
+        t.cut = t.cut || n > 1;
+        for (int j = 0; j < n; ++j) {
+          const int sz = part_floats_of(y, p, i, n, j);
+          if ((i == 0 && j == 0) || run + sz > kARCap) {
+            ++s;
+            run = 0;
+          }
+          if (j == 0) {
+            y.sid[p][i] = s;
+            y.off[p][i] = run;
+          }
+          t.sid[p][i][j] = s;
+          t.off[p][i][j] = run;
+          run += sz;
+          y.sfl[s] = pad(run);
         }
-        y.sid[p][i] = s;
-        y.off[p][i] = run;
-        run += sz;
-        y.sfl[s] = pad(run);
       }
     }
     y.nstg = s + 1;
-    for (int t = 0; t < y.nstg; ++t) y.stg = y.sfl[t] > y.stg ? y.sfl[t] : y.stg;
-    return y;
+    for (int k = 0; k < y.nstg; ++k) y.stg = y.sfl[k] > y.stg ? y.sfl[k] : y.stg;
+    return pl;
   }
-  static constexpr Layout LY = make_layout();
+  static constexpr Plan PL = make_plan();
+  static constexpr Layout LY = PL.ly;
+  static constexpr Parts PT = PL.pt;
   static constexpr int E(int p) { return E_of(LY, p); }
   static constexpr int blo(int p) { return blo_of(LY, p); }  // blocks (re)computed in pass p: those
   static constexpr int bhi(int p) { return bhi_of(LY, p); }  // holding units of degree p; none if blo > bhi
   static constexpr int nb(int p) { return nb_of(LY, p); }
   static constexpr int kt(int p) { return kt_of(LY, p); }    // k-steps over units of degree <= p
   static constexpr int frags(int p, int i) { return frags_of(LY, p, i); }
-  static constexpr int stage_id(int p, int i) { return LY.sid[p][i]; }
-  static constexpr int sub_off(int p, int i) { return LY.off[p][i]; }
+  static constexpr int stage_id(int p, int i) { return LY.sid[p][i]; }  // of the sub-layer's part 0:
+  static constexpr int sub_off(int p, int i) { return LY.off[p][i]; }   // the whole of it unless cut
+  static constexpr bool CUT = PT.cut;
+  static constexpr int parts(int p, int i) { return PT.np[p][i]; }
+  static constexpr int part_stage(int p, int i, int j) { return PT.sid[p][i][j]; }
+  static constexpr int part_off(int p, int i, int j) { return PT.off[p][i][j]; }
+  static constexpr int part_blo(int p, int i, int j) { return i < NHID ? pblo_of(LY, p, PT.np[p][i], j) : 0; }
+  static constexpr int part_nb(int p, int i, int j) { return i < NHID ? pnb_of(LY, p, PT.np[p][i], j) : NOB; }
+  static constexpr int part_frags(int p, int i, int j) {  // (block, k-step) fragments of the part
+    return i == 0 ? part_nb(p, i, j) * KI : part_nb(p, i, j) * kt_of(LY, p);
+  }
+  // pass p's parts in order, k = 0 .. pass_parts(p) - 1 -> (sub-layer, part); uncut: k = the sub-layer
+  static constexpr int pass_parts(int p) {
+    int n = 0;
+    for (int i = 0; i <= NHID; ++i) n += PT.np[p][i];
+    return n;
+  }
+  static constexpr int flat_sub(int p, int k) {
+    int i = 0;
+    for (; k >= PT.np[p][i]; ++i) k -= PT.np[p][i];
+    return i;
+  }
+  static constexpr int flat_part(int p, int k) {
+    for (int i = 0; k >= PT.np[p][i]; ++i) k -= PT.np[p][i];
+    return k;
+  }
+  // the stage of the part before part j of sub-layer i in pass p's order (-1: it opens the pass)
+  static constexpr int prev_stage(int p, int i, int j) {
+    return j > 0 ? PT.sid[p][i][j - 1] : (i > 0 ? PT.sid[p][i - 1][PT.np[p][i - 1] - 1] : -1);
+  }
   static constexpr int stage_floats(int s) { return LY.sfl[s]; }
   static constexpr int NSTG = LY.nstg;
   static constexpr int STG = LY.stg;                  // stage stride = LDS ring slot (floats)
@@ -460,14 +531,15 @@ static void made_ar_pack_layer(const float* flat, const int* perm, float* out) {
   };
   for (int p = 0; p < D; ++p) {
     const int dp = perm[p];
-    for (int i = 0; i <= CF::NHID; ++i) {
-      const int base = CF::stage_id(p, i) * CF::STG + CF::sub_off(p, i);
+    for (int i = 0; i <= CF::NHID; ++i)
+     for (int pt = 0; pt < CF::parts(p, i); ++pt) {  // (one part unless the layout cut the sub-layer)
+      const int base = CF::part_stage(p, i, pt) * CF::STG + CF::part_off(p, i, pt);
       unsigned* st = ou + base;
-      float* bias = out + base + CF::frags(p, i) * CF::OT;
+      float* bias = out + base + (i < CF::NHID ? CF::part_frags(p, i, pt) : CF::frags(p, i)) * CF::OT;
       if (i < CF::NHID) {
         const int kts = i == 0 ? CF::KI : CF::kt(p);
-        for (int bi = 0; bi < CF::nb(p); ++bi) {
-          const int b = CF::blo(p) + bi;
+        for (int bi = 0; bi < CF::part_nb(p, i, pt); ++bi) {
+          const int b = CF::blo(p) + CF::part_blo(p, i, pt) + bi;
           for (int t = 0; t < kts; ++t)
             frag(st + (bi * kts + t) * CF::OT, [&](int m, int kg, int j) -> float {
               const int u = 16 * b + m;
@@ -596,17 +668,20 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::WPE) made_ar_r16_kernel(
       constexpr int p = decltype(pc)::value;
       // pass constants bound to constexpr locals (a constexpr function in a loop bound or argument
       // is not folded reliably: the loops then stay rolled and the fragments go to scratch)
-      constexpr int NBP = CF::nb(p), BLO = CF::blo(p), KT = CF::kt(p);
+      constexpr int KT = CF::kt(p);
       const int dp = dps[p];
       floatx4 o3[CF::NOB];
-      static_for<0, NHID + 1>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        constexpr int SID = CF::stage_id(p, i), OFF = CF::sub_off(p, i);
-        constexpr int OFF_BIAS = OFF + CF::frags(p, i) * CF::OT;
+      // the pass's sub-layers, part by part (a sub-layer is its one part unless the layout cut it,
+      // CfgAR::make_layout; then each part runs over its own blocks BLO .. BLO + NBP - 1)
+      static_for<0, CF::pass_parts(p)>([&](auto kc) {
+        constexpr int i = CF::flat_sub(p, decltype(kc)::value), pt = CF::flat_part(p, decltype(kc)::value);
+        constexpr int SID = CF::part_stage(p, i, pt), OFF = CF::part_off(p, i, pt);
+        constexpr int OFF_BIAS = OFF + (i < NHID ? CF::part_frags(p, i, pt) : CF::frags(p, i)) * CF::OT;
+        constexpr int NBP = i < NHID ? CF::part_nb(p, i, pt) : CF::nb(p), BLO = CF::blo(p) + CF::part_blo(p, i, pt);
         // a stage starts at sub-layer 0 of every pass and wherever the grouping opened a new one
         // (not at OFF == 0: empty sub-layers — no units of degree p, e.g. pass 0 without a
         // context — also sit at offset 0 of their pass's stage)
-        constexpr bool NEW_STAGE = i == 0 || SID != CF::stage_id(p, i > 0 ? i - 1 : 0);
+        constexpr bool NEW_STAGE = SID != CF::prev_stage(p, i, pt);
         if constexpr (NEW_STAGE) {  // it has landed in slot (g & 1)
           constexpr int SF_NEXT = SID + 1 < CF::NSTG ? CF::stage_floats(SID + 1) : CF::stage_floats(0);
           ring_barrier();  // ... and every wave is done with the other slot
@@ -621,13 +696,13 @@ __global__ void __launch_bounds__(64 * CF::NW, CF::WPE) made_ar_r16_kernel(
           ++g;
         }
         const u32x4* c4 = reinterpret_cast<const u32x4*>(cur);
-        auto afrag = [&](int idx) {  // A fragment idx of this sub-layer
+        auto afrag = [&](int idx) {  // A fragment idx of this sub-layer (part)
           const int base = (OFF >> 2) + idx * 128 + lane;
           return Frag2{__builtin_bit_cast(half8, c4[base]), __builtin_bit_cast(half8, c4[base + 64])};
         };
         const float4* bias4 = reinterpret_cast<const float4*>(cur + OFF_BIAS);
         bool done0 = false;
-        if constexpr (p == 0 && !CF::LINEAR) {
+        if constexpr (p == 0 && !CF::LINEAR && !CF::CUT) {
           if (c0mode) {
             // one context vector (naz_ar_flow_pack with pass0): the degree-0 units and the first
             // dim's parameters are per-draw constants, written by the packer in place of this
@@ -1069,11 +1144,14 @@ __global__ void made_ar_pack_kernel(const float* __restrict__ flat, int64_t sfla
   }
   static_for<0, D>([&](auto pc) {
     constexpr int p = decltype(pc)::value;
-    static_for<0, NHID + 1>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      constexpr int base = CF::stage_id(p, i) * CF::STG + CF::sub_off(p, i);
-      constexpr int nfr = CF::frags(p, i);
-      constexpr int size = nfr * CF::OT + 16 * (i < NHID ? CF::nb(p) : CF::NOB);
+    static_for<0, CF::pass_parts(p)>([&](auto kc) {  // (a sub-layer is its one part unless the layout cut it)
+      constexpr int i = CF::flat_sub(p, decltype(kc)::value), pt = CF::flat_part(p, decltype(kc)::value);
+      constexpr int base = CF::part_stage(p, i, pt) * CF::STG + CF::part_off(p, i, pt);
+      constexpr int nfr = i < NHID ? CF::part_frags(p, i, pt) : CF::frags(p, i);
+      constexpr int size = nfr * CF::OT + 16 * CF::part_nb(p, i, pt);
+      // the part's first block (uncut: the call as it was written before parts existed, which the
+      // optimizer folds after inlining — bound to a constant here the existing instances' code changes)
+      [[maybe_unused]] constexpr int pblo = CF::blo(p) + CF::part_blo(p, i, pt);
       if (done || pos < base || pos >= base + size) return;
       done = true;
       const int rel = pos - base;
@@ -1082,7 +1160,7 @@ __global__ void made_ar_pack_kernel(const float* __restrict__ flat, int64_t sfla
         const int r = rel - nfr * CF::OT;
         float v = 0.f;
         if constexpr (i < NHID) {
-          const int u = 16 * (CF::blo(p) + r / 16) + r % 16;
+          const int u = 16 * ((CF::CUT ? pblo : CF::blo(p)) + r / 16) + r % 16;
           if (u < H) v = kSigScale * bl(i)[u];
         } else {
           // (the row test written out where it is r < P: behind a call the optimizer folds it
@@ -1105,7 +1183,7 @@ __global__ void made_ar_pack_kernel(const float* __restrict__ flat, int64_t sfla
           float v = 0.f;
           if constexpr (i < NHID) {
             constexpr int kts = i == 0 ? CF::KI : CF::kt(p);
-            const int t = fr % kts, u = 16 * (CF::blo(p) + fr / kts) + m;
+            const int t = fr % kts, u = 16 * ((CF::CUT ? pblo : CF::blo(p)) + fr / kts) + m;
             if (u < H) {
               if constexpr (i > 0) {
                 const int vv = r16_feat(t, kg, j);
