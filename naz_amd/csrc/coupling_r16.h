@@ -282,6 +282,9 @@ __global__ void coupling_pack_r16_kernel(const float* __restrict__ flat, float* 
 // backward's two waves per SIMD nor the inference kernel's four (in lock step between stage
 // barriers) hide.  bfn(t) returns k-step t's B fragment (formed inside the loop, so the
 // lazy forms' activation VALU still lands between MFMAs).
+// Two triples ahead (a second fragment pair in flight, waits lgkmcnt(4), (2), (0); 8 more VGPRs)
+// was measured in the inference kernel's stage A, GEMM2 and first GEMM3 half: within the run-to-run
+// spread of one triple ahead (profiles/r16_ctx_pf2_ab.txt); in the second GEMM3 half it spills.
 // The NB blocks accumulate into acc[OB .. OB + NB).
 template <int NB, int KB, int OB = 0, int NA, class BFn>
 NAZ_DEV void gemm_r16_pf(floatx4 (&acc)[NA], const float* __restrict__ stage, int lane, BFn&& bfn) {
@@ -554,6 +557,39 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
     if (low != nullptr) slot0[kX6Slot - kR16Rows * 4 + threadIdx.x] = logjac;
   }
 
+  // GEMM1's context k-slots of this lane (0 in the slots that carry none).  The context does not
+  // change from layer to layer: it is loaded here, once, for the range check, for the resident
+  // fragments (cfix below) and as layer 0's values.  Per layer it is loaded again only where fp32
+  // values are still needed:
+  //   * kCtxPerLayer (no resident fragments, or context slots in the last k-step): for layer li + 1
+  //     before layer li's upper spline.  vmcnt retires in order: a context load issued AFTER a
+  //     stage's LDS-DMA (as when it sits in stage A) can only be waited for together with that
+  //     DMA, so stage A would stall on stage B's weights (3 % of the kernel, same-box A/B).
+  //     Issued before the stage-A barrier, the barrier's vmcnt(0) covers them with the stage-A
+  //     weights;
+  //   * otherwise only by the exact-FP32 fallback, inside its branch of stage A (the cold path
+  //     takes that vmcnt wait; issued ahead of stage B's DMA, outside the branch, the load cost
+  //     the fp16 path 36 B of scratch).
+  // The row's address is re-derived from the thread index at each use (tid_now): as 64-bit per-row
+  // pointers kept across the layer loop, the context row and the output row were what the
+  // prefetched GEMM stages' larger live set pushed to scratch.
+  float cpre[CF::KS1 * 8] = {};
+  auto load_ctx = [&]() {
+    if constexpr (CF::C > 0) {
+      const int t_ = tid_now(), q_ = (t_ >> 4) & 3;
+      const int64_t r_ = row_of(t_);
+      const float* cp = ctx + (r_ < B ? r_ : 0) * ldc;
+#pragma unroll
+      for (int t = 0; t < CF::KS1; ++t)
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) {
+          const int col = r16_in_col<CF>(t, q_, jj);
+          cpre[8 * t + jj] = (col >= 0 && col < CF::C) ? cp[col] : 0.f;
+        }
+    }
+  };
+  load_ctx();
+
   // GEMM1 precision path of this workgroup (see the file comment); reduced through ring slot 1
   bool ok = bound < kG1F16Limit;
 #pragma unroll
@@ -561,12 +597,7 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
 #pragma unroll
   for (int u = 0; u < CF::DQ; ++u) ok = ok && fabsf(zu[u]) < kG1F16Limit;
 #pragma unroll
-  for (int t = 0; t < CF::KS1; ++t)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int col = r16_in_col<CF>(t, q, j);
-      if (col >= 0 && col < CF::C) ok = ok && fabsf(ctx[crow * ldc + col]) < kG1F16Limit;
-    }
+  for (int e = 0; e < CF::KS1 * 8; ++e) ok = ok && fabsf(cpre[e]) < kG1F16Limit;
   {
     int* flags = reinterpret_cast<int*>(slot1);
     if (lane == 0) flags[wave] = __all(ok) ? 1 : 0;
@@ -577,6 +608,26 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
     ok = all_ok;
   }
   const bool g1f16 = ok;
+  // The fp16 path's B fragments of GEMM1's pure-context k-steps (t < KS1 - 1), the same in every
+  // layer: split once, resident across the layer loop (8 VGPRs per step, where the per-layer
+  // context load held as many across the upper spline, the kernel's register peak, and sat in
+  // the LDS-DMA ring's vmcnt queue).  Only the last step, which carries this lane's x1 dims, is
+  // formed per layer.  Not read by the exact-FP32 path (whose values may be outside fp16 range).
+  // Not in the sample direction with a lower spline: there hipcc parks the fragments in scratch
+  // and reloads them in stage A (36 B against the per-layer load's 12 B outside the loop).
+  constexpr int NFIX = CF::KS1 - 1;
+  constexpr bool kResident = NFIX > 0 && (DIR_INV || !CF::LOWER);
+  constexpr bool kCtxPerLayer = !kResident || CF::C_LAST > 0;
+  Frag2 cfix[NFIX > 0 ? NFIX : 1];
+  if constexpr (kResident) {
+#pragma unroll
+    for (int t = 0; t < NFIX; ++t) {
+      float v[8];
+#pragma unroll
+      for (int jj = 0; jj < 8; ++jj) v[jj] = cpre[8 * t + jj];
+      cfix[t] = split8_f16(v);
+    }
+  }
 
   const RingSrc ring{packed};
   // stage A of layer l: only what the workgroup's image holds (g1f16 is workgroup-uniform)
@@ -587,28 +638,6 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
   issue_a(slot0, DIR_INV ? (L - 1) : 0);
 
   const RqsConsts<CF::K, DIR_INV> rc(bound);
-  // GEMM1's context k-slots of this lane, loaded for layer li + 1 before layer li's upper spline
-  // (and for layer 0 here).  vmcnt retires in order: a context load issued AFTER a stage's
-  // LDS-DMA (as when it sits in stage A) can only be waited for together with that DMA, so
-  // stage A would stall on stage B's weights (3 % of the kernel, same-box A/B).  Issued before
-  // the stage-A barrier, the barrier's vmcnt(0) covers them with the stage-A weights.
-  // The row's address is re-derived from the thread index at each use (tid_now): as 64-bit per-row
-  // pointers kept across the layer loop, the context row and the output row were what the
-  // prefetched GEMM stages' larger live set pushed to scratch.
-  float cpre[CF::KS1 * 8];
-  auto load_ctx = [&]() {
-    const int t_ = tid_now(), q_ = (t_ >> 4) & 3;
-    const int64_t r_ = row_of(t_);
-    const float* cp = ctx + (r_ < B ? r_ : 0) * ldc;
-#pragma unroll
-    for (int t = 0; t < CF::KS1; ++t)
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) {
-        const int col = r16_in_col<CF>(t, q_, jj);
-        cpre[8 * t + jj] = (col >= 0 && col < CF::C) ? cp[col] : 0.f;
-      }
-  };
-  load_ctx();
   int g = 0;  // global stage counter: stage g lives in slot (g & 1)
   for (int li = 0; li < L; ++li) {
     const int l = DIR_INV ? (L - 1 - li) : li;
@@ -667,17 +696,19 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
             ldsum -= ld;  // ldsum carries the forward maps' log-dets (rqs_table: the inverse's)
           }
         }
-        float in[CF::KS1 * 8];
+        // GEMM1's input k-slots of this lane: context values (cpre) and its own x1 dims
+        auto gemm1_inputs = [&](float (&in)[CF::KS1 * 8]) {
 #pragma unroll
-        for (int t = 0; t < CF::KS1; ++t)
+          for (int t = 0; t < CF::KS1; ++t)
 #pragma unroll
-          for (int jj = 0; jj < 8; ++jj) {
-            const int col = r16_in_col<CF>(t, q, jj);
-            float v = 0.f;
-            if (col >= CF::C) v = zl[(col - CF::C - q * CF::SQ) < CF::SQ ? (col - CF::C - q * CF::SQ) : 0];
-            else if (col >= 0) v = cpre[8 * t + jj];
-            in[8 * t + jj] = v;
-          }
+            for (int jj = 0; jj < 8; ++jj) {
+              const int col = r16_in_col<CF>(t, q, jj);
+              float v = 0.f;
+              if (col >= CF::C) v = zl[(col - CF::C - q * CF::SQ) < CF::SQ ? (col - CF::C - q * CF::SQ) : 0];
+              else if (col >= 0) v = cpre[8 * t + jj];
+              in[8 * t + jj] = v;
+            }
+        };
         {
           const float4* b4 = reinterpret_cast<const float4*>(cur + CF::A_BIAS);
 #pragma unroll
@@ -687,13 +718,22 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
           }
         }
         if (g1f16) {
+          float in[CF::KS1 * 8];
+          gemm1_inputs(in);
           Frag2 bf[CF::KS1];
-          gemm1_frags<CF>(in, bf);
+          gemm1_frags<CF>(in, bf);  // (resident: only the last step's split survives)
+          if constexpr (kResident) {
+#pragma unroll
+            for (int t = 0; t < NFIX; ++t) bf[t] = cfix[t];
+          }
           __builtin_amdgcn_s_setprio(1);
           gemm1_r16<CF, true>(acc1, cur + CF::A_W, lane, bf);
           __builtin_amdgcn_s_setprio(0);
         } else {
           // exact fp32: 8 KS1 k-steps of 4; k-step s on this lane = slot (s / 8, s % 8)
+          if constexpr (!kCtxPerLayer) load_ctx();  // (see cpre)
+          float in[CF::KS1 * 8];
+          gemm1_inputs(in);
           const float4* p4 = reinterpret_cast<const float4*>(cur + CF::A_W);
 #pragma unroll
           for (int s4 = 0; s4 < 2 * CF::KS1; ++s4)
@@ -742,7 +782,9 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
     });
 
     // ---------------- upper spline on this quarter's remaining dims (next layer's stage A in flight)
-    if (li + 1 < L) load_ctx();
+    if constexpr (kCtxPerLayer) {
+      if (li + 1 < L) load_ctx();
+    }
     static_for<CF::SPLIT3 ? 1 : 0, CF::DQ>([&](auto uc) { upper(uc); });
 #ifdef NAZ_DEBUG_NONFINITE
     {
@@ -755,7 +797,7 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
     }
 #endif
   }
-  const Where w = where();  // re-derived after the layer loop (see load_ctx)
+  const Where w = where();  // re-derived after the layer loop (see cpre)
   if constexpr (VAR == 1) {  // P[0] = z
     if (w.valid) {
       float* st = states + w.row * CF::D;
