@@ -600,7 +600,10 @@ __global__ void __launch_bounds__(kR16Rows * 4, 4) coupling_r16_kernel(
   for (int e = 0; e < CF::KS1 * 8; ++e) ok = ok && fabsf(cpre[e]) < kG1F16Limit;
   {
     int* flags = reinterpret_cast<int*>(slot1);
-    if (lane == 0) flags[wave] = __all(ok) ? 1 : 0;
+    // the vote is taken with every lane active: inside the lane-0 branch __all sees lane 0 alone,
+    // and a wave whose lane 0 was in range sent an out-of-range row down the fp16 path (NaN)
+    const bool wave_ok = __all(ok);
+    if (lane == 0) flags[wave] = wave_ok ? 1 : 0;
     __syncthreads();
     bool all_ok = true;
 #pragma unroll

@@ -125,7 +125,8 @@ __global__ void __launch_bounds__(kX6Rows * 2, kX6Waves / 2) coupling_w32_kernel
   for (int k = 0; k < CF::CT * 8; ++k) ok = ok && fabsf(cv[k]) < kG1F16Limit;
   {
     int* flags = reinterpret_cast<int*>(slot1);
-    if (lane == 0) flags[wave] = __all(ok) ? 1 : 0;
+    const bool wave_ok = __all(ok);  // every lane votes (inside the lane-0 branch only lane 0 would)
+    if (lane == 0) flags[wave] = wave_ok ? 1 : 0;
     __syncthreads();
     bool all_ok = true;
 #pragma unroll

@@ -361,7 +361,8 @@ __global__ void __launch_bounds__(kX6Rows * 2, kX6Waves / 2) coupling_x6_kernel(
     // workgroup AND through ring slot 1 (unused until the first in-loop barrier; static LDS
     // for __syncthreads_and would push the workgroup past 80 KB = one workgroup per CU)
     int* flags = reinterpret_cast<int*>(slot1);
-    if (lane == 0) flags[wave] = __all(ok) ? 1 : 0;
+    const bool wave_ok = __all(ok);  // every lane votes (inside the lane-0 branch only lane 0 would)
+    if (lane == 0) flags[wave] = wave_ok ? 1 : 0;
     __syncthreads();
     bool all_ok = true;
 #pragma unroll

@@ -425,9 +425,9 @@ def _bwd_layer(f, state, ctx, g_in, layer=2, g_lp_value=-1.0 / (1 << 16)):
     B = state.shape[0]
     ncol = ops.coupling_dp3_columns(d).numel()
     bufs = {k: torch.empty((B, n), device=DEV) for k, n in
-            (("h1", 128), ("h2", 128), ("dp1", 128), ("dp2", 128), ("dp3", ncol), ("x0", 40))}
+            (("h1", d.H), ("h2", d.H), ("dp1", d.H), ("dp2", d.H), ("dp3", ncol), ("x0", d.C + d.S))}
     g_out = torch.empty_like(g_in)
-    g_low = torch.zeros((8 * 23,), device=DEV)
+    g_low = torch.zeros((d.S * (3 * d.K - 1),), device=DEV)
     g_lp = torch.full((B,), g_lp_value, device=DEV)
     ops.coupling_bwd_layer(d, packed, pbwd, flat, layer, state, ctx, g_in, g_lp, bufs, g_out, g_low)
     torch.cuda.synchronize()
