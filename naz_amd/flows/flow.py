@@ -218,7 +218,7 @@ class _FusedAR:
         """The NLL step on a fused backward: an affine ("maf") flow on made_ar_bwd.h's affine instances
         (flows/maf_grad.py) or the GEMM-composed wide backward, or a spline ("nsa") flow at the
         compiled shape of made_ar_bwd.h's spline instance (naz's own D=4 | C=2, H=[128,128], K=8;
-        flows/nsa_grad.py: a saved-state forward plus one backward launch per layer).  Conditions:
+        flows/maf_grad.py's NsaGrad: a saved-state forward plus one backward launch per layer).  Conditions:
         rows and context inside the f16 split's range, no gradient wanted for x or the context
         (train's data).  Everything else keeps the autograd walk: other nsa shapes, order="linear"
         (kind "nsa_linear": fused log_prob and sample only), active dropout, Permute layers and
@@ -249,13 +249,12 @@ class _FusedAR:
         cz = any(bool(getattr(n, "clip_zero_grad", False)) for n in nets)  # jnp.clip's gradient (bflow)
         sig = tuple((t.data_ptr(), t._version) for t in ts) + (cache_epoch(), cz)
         if getattr(self, "_mg", None) is None or self._mg[0] != sig:
-            from .maf_grad import MafGrad
+            from .maf_grad import MafGrad, NsaGrad
             from .maf_grad_wide import WideMafGrad
             mask = torch.cat([t for n in nets for l in n.layers
                               for t in (l.mask.detach().reshape(-1).float(), torch.ones_like(l.bias.detach()))])
             perm = np.stack([n.permutation.detach().cpu().numpy() for n in nets]).astype(np.int32)
             if self.kind == "nsa":
-                from .nsa_grad import NsaGrad
                 cls = NsaGrad
             else:
                 cls = MafGrad if ops.ar_flow_bwd_supported(self.desc) else WideMafGrad
@@ -431,7 +430,7 @@ class _MafTrainFn(torch.autograd.Function):
     """NormalizingFlow.log_prob of a maf or nsa flow under autograd at the fused backward's shapes
     (naz train's loss, train_flows.py:195, 208): forward = the fused inverse kernel with every
     layer's output saved; backward = one fused backward launch per layer + batched dW
-    (flows/maf_grad.py, flows/nsa_grad.py: generic over the grad object)."""
+    (flows/maf_grad.py: generic over the grad object)."""
 
     @staticmethod
     def forward(ctx, x, context, plan, *params):

@@ -1026,7 +1026,77 @@ def ar_flow_log_prob(d: ArDesc, packed: Tensor, x: Tensor, context: Optional[Ten
     return out
 
 
-# ----------------------------------------------------------------------------- fused maf backward (§8f rank 1)
+# ----------------------------------------------------------------------------- fused maf / nsa backward
+# One host path behind the ar_flow_* (maf, §8f rank 1) and spline_ar_flow_* (nsa) entries: ``fam`` is that
+# prefix, which the error texts (the public function's name) and the naz_* symbols carry.
+_AR_BWD_DIMS = ("n_hidden", "HP", "XA", "XB", "X0W", "rows")
+_SPLINE_AR_BWD_DIMS = _AR_BWD_DIMS[:5] + ("GOW", "rows")
+
+
+def _ar_bwd_dims(fam: str, d: ArDesc, keys: Tuple[str, ...]) -> dict:
+    name = fam + "_bwd_dims"
+    out = np.zeros(len(keys), dtype=np.int32)
+    check(getattr(lib(), "naz_" + name)(d, out.ctypes.data), name)
+    return dict(zip(keys, (int(v) for v in out)))
+
+
+def _ar_pack_bwd(fam: str, d: ArDesc, flat: Tensor, mask: Optional[Tensor]) -> Tensor:
+    name = fam + "_pack_bwd"
+    dev = _dev(flat, mask)
+    flat = flat.reshape(-1).contiguous()
+    n = int(getattr(lib(), f"naz_{fam}_bwd_packed_bytes")(d)) // 4
+    if n <= 0:
+        raise RuntimeError(f"naz_amd {name}: unsupported descriptor")
+    if mask is not None and (mask.numel() != flat.numel() or not mask.is_contiguous()):
+        raise ValueError(f"{name}: mask must be a contiguous tensor shaped like flat")
+    out = torch.empty(n, device=dev, dtype=torch.float32)
+    check(getattr(lib(), "naz_" + name)(d, _p(flat), _p(mask), _p(out), _stream(dev)), name)
+    return track_image(out)
+
+
+def _ar_bwd_layer(fam: str, dims, out_width: str, d: ArDesc, packed_fwd: Tensor, packed_bwd: Tensor,
+                  perm: Tensor, layer: int, states: tuple, context: Optional[Tensor], g_in: Tensor,
+                  g_lp: Optional[Tensor], bufs: List[Tensor], g_out: Tensor) -> None:
+    """The layer call of both families.  ``states``: ((argument name, [B, D] tensor), ...) in the
+    entry's order; ``dims``: the family's *_bwd_dims; ``out_width``: its key of the last operand's
+    (gout's) width."""
+    name = fam + "_bwd_layer"
+    sts = tuple(t for _, t in states)
+    dev = _dev(packed_fwd, packed_bwd, *sts, context, g_in, g_lp, g_out)
+    if perm.dtype != torch.int32 or perm.device != dev or perm.shape != (d.L, d.D):
+        raise ValueError(f"{name}: perm must be an int32 [{d.L}, {d.D}] tensor on {dev}")
+    B = sts[0].shape[0]
+    context, ldc = _ctx_arg(context, B)
+    for t in sts + (g_in, g_out, perm) + tuple(b for b in bufs if b is not None) + \
+            ((g_lp,) if g_lp is not None else ()):
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: buffers must be contiguous")
+    if not (0 <= int(layer) < d.L):
+        raise ValueError(f"{name}: layer {layer} outside [0, {d.L})")
+    for arg, t in states + (("g_in", g_in), ("g_out", g_out)):
+        if t.dim() != 2 or t.shape[0] != B or t.shape[1] != d.D or t.dtype != torch.float32:
+            raise ValueError(f"{name}: {arg} must be float32 [{B}, {d.D}], got {tuple(t.shape)}")
+    if g_lp is not None and (g_lp.numel() != B or g_lp.dtype != torch.float32):
+        raise ValueError(f"{name}: g_lp must be float32 [{B}]")
+    # bufs (include/naz_hip.h): x0, then per hidden layer (h_i, h_i split tail), then dp_i, then gout
+    dm = dims(d)
+    NH, HP, X0W, XA, XB = dm["n_hidden"], dm["HP"], dm["X0W"], dm["XA"], dm["XB"]
+    if len(bufs) != 2 + 3 * NH:
+        raise ValueError(f"{name}: {2 + 3 * NH} operand buffers expected, got {len(bufs)}")
+    widths = [X0W] + [w for _ in range(NH) for w in (XA, XB)] + [HP] * NH + [dm[out_width]]
+    for k, (t, w) in enumerate(zip(bufs, widths)):
+        if t is None:
+            if w != 0 and not (1 <= k <= 2 * NH and k % 2 == 0 and XB == 0):
+                raise ValueError(f"{name}: operand buffer {k} is required")
+            continue
+        if t.dim() != 2 or t.shape[0] < B or t.shape[1] != w or t.dtype != torch.float32 or t.device != dev:
+            raise ValueError(f"{name}: operand buffer {k} must be float32 [>= {B}, {w}] on {dev}, "
+                             f"got {tuple(t.shape)}")
+    ptrs = (C.c_void_p * len(bufs))(*[_p(b) for b in bufs])
+    check(getattr(lib(), "naz_" + name)(d, _p(packed_fwd), _p(packed_bwd), _p(perm), int(layer), *[_p(t) for t in sts],
+                                        _p(context), ldc, _p(g_in), _p(g_lp), ptrs, _p(g_out), B, _stream(dev)), name)
+
+
 def ar_flow_bwd_supported(d: ArDesc) -> bool:
     """The fused maf backward (made_ar_bwd.h) is compiled for this shape."""
     return int(lib().naz_ar_flow_bwd_packed_bytes(d)) > 0
@@ -1034,23 +1104,12 @@ def ar_flow_bwd_supported(d: ArDesc) -> bool:
 
 def ar_flow_bwd_dims(d: ArDesc) -> dict:
     """Operand widths of naz_ar_flow_bwd_layer (include/naz_hip.h)."""
-    out = np.zeros(6, dtype=np.int32)
-    check(lib().naz_ar_flow_bwd_dims(d, out.ctypes.data), "ar_flow_bwd_dims")
-    return dict(zip(("n_hidden", "HP", "XA", "XB", "X0W", "rows"), (int(v) for v in out)))
+    return _ar_bwd_dims("ar_flow", d, _AR_BWD_DIMS)
 
 
 def ar_flow_pack_bwd(d: ArDesc, flat: Tensor, mask: Optional[Tensor] = None) -> Tensor:
     """Per-layer backward images (naz_ar_flow_pack_bwd) of one flow's flat [L * per] parameters."""
-    dev = _dev(flat, mask)
-    flat = flat.reshape(-1).contiguous()
-    n = int(lib().naz_ar_flow_bwd_packed_bytes(d)) // 4
-    if n <= 0:
-        raise RuntimeError("naz_amd ar_flow_pack_bwd: unsupported descriptor")
-    if mask is not None and (mask.numel() != flat.numel() or not mask.is_contiguous()):
-        raise ValueError("ar_flow_pack_bwd: mask must be a contiguous tensor shaped like flat")
-    out = torch.empty(n, device=dev, dtype=torch.float32)
-    check(lib().naz_ar_flow_pack_bwd(d, _p(flat), _p(mask), _p(out), _stream(dev)), "ar_flow_pack_bwd")
-    return track_image(out)
+    return _ar_pack_bwd("ar_flow", d, flat, mask)
 
 
 def ar_flow_log_prob_train(d: ArDesc, packed: Tensor, x: Tensor, context: Optional[Tensor], states: Tensor,
@@ -1076,42 +1135,10 @@ def ar_flow_bwd_layer(d: ArDesc, packed_fwd: Tensor, packed_bwd: Tensor, perm: T
                       g_out: Tensor) -> None:
     """Layer ``layer``'s fused maf backward (naz_ar_flow_bwd_layer): g_in = dL/ds_l -> g_out =
     dL/ds_{l+1} and the weight-gradient operands ``bufs`` (include/naz_hip.h order)."""
-    dev = _dev(packed_fwd, packed_bwd, state, context, g_in, g_lp, g_out)
-    if perm.dtype != torch.int32 or perm.device != dev or perm.shape != (d.L, d.D):
-        raise ValueError(f"ar_flow_bwd_layer: perm must be an int32 [{d.L}, {d.D}] tensor on {dev}")
-    B = state.shape[0]
-    context, ldc = _ctx_arg(context, B)
-    for t in (state, g_in, g_out, perm) + tuple(b for b in bufs if b is not None) + ((g_lp,) if g_lp is not None else ()):
-        if not t.is_contiguous():
-            raise ValueError("ar_flow_bwd_layer: buffers must be contiguous")
-    if not (0 <= int(layer) < d.L):
-        raise ValueError(f"ar_flow_bwd_layer: layer {layer} outside [0, {d.L})")
-    for name, t in (("state", state), ("g_in", g_in), ("g_out", g_out)):
-        if t.dim() != 2 or t.shape[0] != B or t.shape[1] != d.D or t.dtype != torch.float32:
-            raise ValueError(f"ar_flow_bwd_layer: {name} must be float32 [{B}, {d.D}], got {tuple(t.shape)}")
-    if g_lp is not None and (g_lp.numel() != B or g_lp.dtype != torch.float32):
-        raise ValueError(f"ar_flow_bwd_layer: g_lp must be float32 [{B}]")
-    # bufs (include/naz_hip.h): x0, then per hidden layer (h_i, h_i split tail), then dp_i, then gout
-    dm = ar_flow_bwd_dims(d)
-    NH, HP, X0W, XA, XB = dm["n_hidden"], dm["HP"], dm["X0W"], dm["XA"], dm["XB"]
-    if len(bufs) != 2 + 3 * NH:
-        raise ValueError(f"ar_flow_bwd_layer: {2 + 3 * NH} operand buffers expected, got {len(bufs)}")
-    widths = [X0W] + [w for _ in range(NH) for w in (XA, XB)] + [HP] * NH + [X0W]
-    for k, (t, w) in enumerate(zip(bufs, widths)):
-        if t is None:
-            if w != 0 and not (1 <= k <= 2 * NH and k % 2 == 0 and XB == 0):
-                raise ValueError(f"ar_flow_bwd_layer: operand buffer {k} is required")
-            continue
-        if t.dim() != 2 or t.shape[0] < B or t.shape[1] != w or t.dtype != torch.float32 or t.device != dev:
-            raise ValueError(f"ar_flow_bwd_layer: operand buffer {k} must be float32 [>= {B}, {w}] on {dev}, "
-                             f"got {tuple(t.shape)}")
-    ptrs = (C.c_void_p * len(bufs))(*[_p(b) for b in bufs])
-    check(lib().naz_ar_flow_bwd_layer(d, _p(packed_fwd), _p(packed_bwd), _p(perm), int(layer), _p(state),
-                                      _p(context), ldc, _p(g_in), _p(g_lp), ptrs, _p(g_out), B, _stream(dev)),
-          "ar_flow_bwd_layer")
+    _ar_bwd_layer("ar_flow", ar_flow_bwd_dims, "X0W", d, packed_fwd, packed_bwd, perm, layer, (("state", state),),
+                  context, g_in, g_lp, bufs, g_out)
 
 
-# ----------------------------------------------------------------------------- fused nsa backward
 def spline_ar_flow_bwd_supported(d: ArDesc) -> bool:
     """The fused nsa backward (made_ar_bwd.h, spline instance) is compiled for this shape."""
     return int(lib().naz_spline_ar_flow_bwd_packed_bytes(d)) > 0
@@ -1119,23 +1146,12 @@ def spline_ar_flow_bwd_supported(d: ArDesc) -> bool:
 
 def spline_ar_flow_bwd_dims(d: ArDesc) -> dict:
     """Operand widths of naz_spline_ar_flow_bwd_layer (include/naz_hip.h)."""
-    out = np.zeros(7, dtype=np.int32)
-    check(lib().naz_spline_ar_flow_bwd_dims(d, out.ctypes.data), "spline_ar_flow_bwd_dims")
-    return dict(zip(("n_hidden", "HP", "XA", "XB", "X0W", "GOW", "rows"), (int(v) for v in out)))
+    return _ar_bwd_dims("spline_ar_flow", d, _SPLINE_AR_BWD_DIMS)
 
 
 def spline_ar_flow_pack_bwd(d: ArDesc, flat: Tensor, mask: Optional[Tensor] = None) -> Tensor:
     """Per-layer backward images (naz_spline_ar_flow_pack_bwd) of one nsa flow's flat [L * per] parameters."""
-    dev = _dev(flat, mask)
-    flat = flat.reshape(-1).contiguous()
-    n = int(lib().naz_spline_ar_flow_bwd_packed_bytes(d)) // 4
-    if n <= 0:
-        raise RuntimeError("naz_amd spline_ar_flow_pack_bwd: unsupported descriptor")
-    if mask is not None and (mask.numel() != flat.numel() or not mask.is_contiguous()):
-        raise ValueError("spline_ar_flow_pack_bwd: mask must be a contiguous tensor shaped like flat")
-    out = torch.empty(n, device=dev, dtype=torch.float32)
-    check(lib().naz_spline_ar_flow_pack_bwd(d, _p(flat), _p(mask), _p(out), _stream(dev)), "spline_ar_flow_pack_bwd")
-    return track_image(out)
+    return _ar_pack_bwd("spline_ar_flow", d, flat, mask)
 
 
 def spline_ar_flow_log_prob_train(d: ArDesc, packed: Tensor, x: Tensor, context: Optional[Tensor], states: Tensor,
@@ -1161,39 +1177,8 @@ def spline_ar_flow_bwd_layer(d: ArDesc, packed_fwd: Tensor, packed_bwd: Tensor, 
     """Layer ``layer``'s fused nsa backward (naz_spline_ar_flow_bwd_layer): state_out = s_l, state_in =
     s_{l+1} (the flow's input for the last layer); g_in = dL/ds_l -> g_out = dL/ds_{l+1} and the
     weight-gradient operands ``bufs`` (include/naz_hip.h order)."""
-    dev = _dev(packed_fwd, packed_bwd, state_out, state_in, context, g_in, g_lp, g_out)
-    if perm.dtype != torch.int32 or perm.device != dev or perm.shape != (d.L, d.D):
-        raise ValueError(f"spline_ar_flow_bwd_layer: perm must be an int32 [{d.L}, {d.D}] tensor on {dev}")
-    B = state_out.shape[0]
-    context, ldc = _ctx_arg(context, B)
-    for t in (state_out, state_in, g_in, g_out, perm) + tuple(b for b in bufs if b is not None) + \
-            ((g_lp,) if g_lp is not None else ()):
-        if not t.is_contiguous():
-            raise ValueError("spline_ar_flow_bwd_layer: buffers must be contiguous")
-    if not (0 <= int(layer) < d.L):
-        raise ValueError(f"spline_ar_flow_bwd_layer: layer {layer} outside [0, {d.L})")
-    for name, t in (("state_out", state_out), ("state_in", state_in), ("g_in", g_in), ("g_out", g_out)):
-        if t.dim() != 2 or t.shape[0] != B or t.shape[1] != d.D or t.dtype != torch.float32:
-            raise ValueError(f"spline_ar_flow_bwd_layer: {name} must be float32 [{B}, {d.D}], got {tuple(t.shape)}")
-    if g_lp is not None and (g_lp.numel() != B or g_lp.dtype != torch.float32):
-        raise ValueError(f"spline_ar_flow_bwd_layer: g_lp must be float32 [{B}]")
-    dm = spline_ar_flow_bwd_dims(d)
-    NH, HP, X0W, XA, XB, GOW = dm["n_hidden"], dm["HP"], dm["X0W"], dm["XA"], dm["XB"], dm["GOW"]
-    if len(bufs) != 2 + 3 * NH:
-        raise ValueError(f"spline_ar_flow_bwd_layer: {2 + 3 * NH} operand buffers expected, got {len(bufs)}")
-    widths = [X0W] + [w for _ in range(NH) for w in (XA, XB)] + [HP] * NH + [GOW]
-    for k, (t, w) in enumerate(zip(bufs, widths)):
-        if t is None:
-            if w != 0 and not (1 <= k <= 2 * NH and k % 2 == 0 and XB == 0):
-                raise ValueError(f"spline_ar_flow_bwd_layer: operand buffer {k} is required")
-            continue
-        if t.dim() != 2 or t.shape[0] < B or t.shape[1] != w or t.dtype != torch.float32 or t.device != dev:
-            raise ValueError(f"spline_ar_flow_bwd_layer: operand buffer {k} must be float32 [>= {B}, {w}] on {dev}, "
-                             f"got {tuple(t.shape)}")
-    ptrs = (C.c_void_p * len(bufs))(*[_p(b) for b in bufs])
-    check(lib().naz_spline_ar_flow_bwd_layer(d, _p(packed_fwd), _p(packed_bwd), _p(perm), int(layer), _p(state_out),
-                                             _p(state_in), _p(context), ldc, _p(g_in), _p(g_lp), ptrs, _p(g_out), B,
-                                             _stream(dev)), "spline_ar_flow_bwd_layer")
+    _ar_bwd_layer("spline_ar_flow", spline_ar_flow_bwd_dims, "GOW", d, packed_fwd, packed_bwd, perm, layer,
+                  (("state_out", state_out), ("state_in", state_in)), context, g_in, g_lp, bufs, g_out)
 
 
 # ----------------------------------------------------------------------------- a10: fused NLL step

@@ -1,4 +1,4 @@
-"""A/B of the nsa NLL step: the fused spline backward (flows/nsa_grad.py) against the autograd walk
+"""A/B of the nsa NLL step: the fused spline backward (flows/maf_grad.py, NsaGrad) against the autograd walk
 (NAZ_TRAIN_FUSED=0, the path before it existed), same process, same weights and rows, interleaved.
 
     python scripts/nsa_train_bench.py [--rows 262144 10752] [--layers 8] [--reps 3] [--iters 5]

@@ -1,4 +1,4 @@
-"""GPU: the nsa NLL step on the fused spline backward (flows/nsa_grad.py: the saved-state inverse
+"""GPU: the nsa NLL step on the fused spline backward (flows/maf_grad.py, NsaGrad: the saved-state inverse
 kernel, made_ar_spline_bwd_kernel per layer, batched dW) at naz's own nsa shape D=4 | C=2,
 H=[128,128], K=8 — against the oracle's float64 / float32 autograd (tests/parity.py) and the
 autograd walk (NAZ_TRAIN_FUSED=0), identity tails, row independence, bounds, Adam steps, a captured
